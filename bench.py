@@ -24,11 +24,31 @@ torchrun) with B simulated relays, each a closed loop of gRPC ``StreamAudio``
 calls (wake-word chunk, 100 ms PCM16 chunks, end of speech), per-relay-group
 arbitration with the single-relay bypass (every bench relay is alone in its
 group; ``--no-bypass`` waits out the window), the GPU voice processor,
-voice-event writes to SQLite and the command queue on NATS. After the timed
-steps, ``--window-steps`` more run with the reference's 300 ms window
-(``window_300ms``, a secondary field). ``closed``: B closed-loop streams per
-GPU submit straight into the voice pipeline (no gRPC). ``batch``: lockstep
-batches of B.
+voice-event writes to SQLite and the command queue on NATS. ``closed``: B
+closed-loop streams per GPU submit straight into the voice pipeline (no gRPC).
+``batch``: lockstep batches of B.
+
+A plain run sets up, warms up, times ``--steps`` steps and prints the result
+line. ``--full`` adds the measurements that take runs of their own: after the
+timed steps, ``--window-steps`` more run with the reference's 300 ms window
+(``window_300ms``, a secondary field, null without ``--full``). The timed steps
+draw the same utterances with and without ``--full``.
+
+``--dump-outputs DIR`` writes what the last timed step returned to its callers
+(one row per stream, float32 / float64 ``.npy``): ``rms`` (fused PCM
+convert/RMS), ``stt_text`` (the transcript: its length, then its code points,
+-1 padded), ``stt_confidence``, ``commands`` (parsed count, expected count,
+queue success) and ``encoder_xkv`` (256 fixed, seeded elements of the Whisper
+encoder's result for the utterance: the last decoder layer's cross-attention
+K|V, through log-mel, every encoder layer and the K|V GEMM). The inputs depend
+on the arguments alone. Between two runs of one build on an MI355X ``rms``
+agreed to an ulp (its sum of squares is accumulated atomically),
+``encoder_xkv`` to bf16 rounding, the other arrays exactly. The decoded JSON
+of each reply goes to ``llm_replies.jsonl``, as text and not as an array: its
+free fields are greedy tokens of a random-init model, whose near-tied logits
+fall differently whenever the continuous batch is composed differently. Two
+runs of one build agreed on ``is_multi`` and on every first intent, and
+differed from the first command's confidence digits on in 6 of 8 replies.
 
 ``--gpus N`` must match the launch: under torchrun WORLD_SIZE must equal N
 (else exit 2); without torchrun and N > 1 the bench launches
@@ -41,6 +61,7 @@ import argparse
 import asyncio
 import json
 import os
+import re
 import sys
 import threading
 import time
@@ -200,6 +221,102 @@ def hub_summary(srv, recs: list, args, events_before: int = 0) -> tuple[float | 
                    "window_ms": args.window_ms}
 
 
+DUMP_TEXT_WIDTH = 512
+PROBE_POINTS = 256
+
+
+def _relay_order(name: str) -> list:
+    return [int(p) if p.isdigit() else p for p in re.split(r"(\d+)", name)]
+
+
+def _code_points(texts: list[str], width: int = DUMP_TEXT_WIDTH) -> np.ndarray:
+    """[n, 1 + width]: each text's length, then its code points (-1 padded)."""
+    assert all(len(t) <= width for t in texts), "text longer than the dump's row"
+    out = np.full((len(texts), 1 + width), -1.0, dtype=np.float32)
+    for i, t in enumerate(texts):
+        out[i, 0] = len(t)
+        out[i, 1:1 + len(t)] = [ord(c) for c in t]
+    return out
+
+
+class EncoderProbe:
+    """``--dump-outputs``: what the Whisper encoder computed for the last timed
+    utterances - ``PROBE_POINTS`` fixed (seeded) elements of the last decoder
+    layer's cross-attention K|V rows of each utterance, read from the engine's
+    slot when the utterance's transcription finishes (the slot is reused by
+    later arrivals). Only utterances whose transcript is in ``wanted`` are
+    read: each read waits for the STT stream, so the timed steps before the
+    last one run as without the probe."""
+
+    def __init__(self, stt: STTEngine, wanted: set[str], seed: int):
+        self.stt, self.wanted = stt, wanted
+        self.samples: dict[str, np.ndarray] = {}
+        T, width = stt.cfg.n_audio_ctx, stt.xkv[-1].shape[1]
+        rng = np.random.default_rng(seed)
+        self.T = T
+        self.rows = torch.from_numpy(rng.integers(0, T, PROBE_POINTS)).to(stt.device)
+        self.cols = torch.from_numpy(rng.integers(0, width, PROBE_POINTS)).to(stt.device)
+        submit_batch, transcribe = stt.submit_batch, stt.transcribe
+
+        def probed_submit(reqs, on_done=None):
+            def done(r):                      # STT scheduler thread, its stream
+                self.read(r)
+                if on_done is not None:
+                    on_done(r)
+            return submit_batch(reqs, done)
+
+        def probed_transcribe(reqs, device_pcm=None):
+            out = transcribe(reqs, device_pcm)
+            for r in reqs:
+                self.read(r)
+            return out
+        stt.submit_batch, stt.transcribe = probed_submit, probed_transcribe
+
+    def read(self, r) -> None:
+        if r.transcript in self.wanted and r.slot >= 0:
+            kv = self.stt.xkv[-1][r.slot * self.T + self.rows, self.cols]
+            self.samples[r.transcript] = kv.float().cpu().numpy()
+
+    def rows_for(self, jobs: list) -> np.ndarray:
+        return np.stack([self.samples[j.transcript_hint] for j in jobs]).astype(np.float32)
+
+
+def last_step_outputs(jobs: list, probe: EncoderProbe | None = None) -> tuple[dict, list[dict]]:
+    """What the last timed step returned, one row per stream (streams in
+    relay order): every stream's last finished job. The arrays, and the
+    decoded replies (text: not reproducible, see the module docstring)."""
+    last: dict[str, PipelineJob] = {}
+    for j in jobs:
+        last[j.relay_id] = j
+    rows = [last[r] for r in sorted(last, key=_relay_order)]
+    out = {"rms": np.array([j.rms for j in rows], dtype=np.float32),
+           "commands": np.array([[j.n_commands, j.n_expected,
+                                  float(j.queue is not None and j.queue.success)] for j in rows],
+                                dtype=np.float64).reshape(-1, 3)}
+    out["stt_text"] = _code_points([j.transcription.text if j.transcription else j.raw_text
+                                    for j in rows])
+    out["stt_confidence"] = np.array([j.transcription.confidence_estimate if j.transcription else 0.0
+                                      for j in rows], dtype=np.float32)
+    if probe is not None:
+        out["encoder_xkv"] = probe.rows_for(rows)
+    return out, [{"relay": j.relay_id, "llm_output": j.llm_output} for j in rows]
+
+
+def dump_outputs(path: str, arrays: dict[str, np.ndarray], replies: list[dict],
+                 rank: int = 0) -> None:
+    """``--dump-outputs``: ``<name>.npy`` per array and the decoded replies as
+    ``llm_replies.jsonl`` (``<name>.rank<r>.*`` on the other ranks of a
+    multi-GPU run)."""
+    os.makedirs(path, exist_ok=True)
+    sfx = f".rank{rank}" if rank else ""
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64)
+        np.save(os.path.join(path, name + sfx + ".npy"), a)
+    with open(os.path.join(path, "llm_replies" + sfx + ".jsonl"), "w") as f:
+        for r in replies:
+            f.write(json.dumps(r) + "\n")
+
+
 def run_hub_dp(args) -> int:
     """``--mode hub`` over ``--gpus N`` (or with ``--tts``): the served hub as
     deployed for BASELINE config 4 - one front-end process (gRPC relays,
@@ -240,6 +357,7 @@ def run_hub_dp(args) -> int:
     uniq = make_unique(args.seed, counts)
     hints: dict[str, str] = {}
     hub_recs: dict[str, list] = {}
+    last_reply: dict = {}      # relay -> the last timed utterance's gRPC response
 
     async def main() -> dict:
         srv = HubServer(cfg, skills_dir=os.path.join(tmp, "skills"),
@@ -275,6 +393,8 @@ def run_hub_dp(args) -> int:
                 if record:
                     hub_recs.setdefault(relay, []).append(
                         [u.n_commands, float(bool(got) and got[-1].success), lat])
+                    if got:
+                        last_reply[relay] = got[-1]
 
         async def run(n: int, record: bool) -> None:
             async with grpc.aio.insecure_channel(f"127.0.0.1:{srv.grpc_port}") as ch:
@@ -306,6 +426,19 @@ def run_hub_dp(args) -> int:
             await counter.close()
             await srv.stop()
         r = np.array(recs, dtype=np.float64).reshape(-1, 4)
+        if args.dump_outputs:
+            # the front end sees what the relays do: every relay's last reply
+            # (the engines' own arrays stay in the worker processes)
+            names = list(hub_recs)
+            order = sorted(range(len(names)), key=lambda i: _relay_order(names[i]))
+            per = r.reshape(len(names), -1, 4)[:, -1, :3]
+            got = [last_reply.get(names[i]) for i in order]
+            dump_outputs(args.dump_outputs,
+                         {"commands": np.ascontiguousarray(per[order]),
+                          "stt_text": _code_points([g.transcription if g else "" for g in got])},
+                         [{"relay": names[i], "command": g.command if g else "",
+                           "response_text": g.response_text if g else ""}
+                          for i, g in zip(order, got)])
         return {"elapsed": elapsed, "slope": slope, "hub": hub_stats, "init_s": t_init,
                 "ok": float(r[:, 2].mean()) if len(r) else 0.0,
                 "match": float((r[:, 0] == r[:, 1]).mean()) if len(r) else 0.0}
@@ -404,8 +537,12 @@ def main(argv=None) -> int:
     ap.add_argument("--window-ms", type=float, default=300.0,
                     help="--mode hub: arbitration window (the reference's 300 ms)")
     ap.add_argument("--window-steps", type=int, default=4,
-                    help="--mode hub with bypass: utterances per relay timed afterwards with the "
-                         "bypass off (the window_300ms secondary field; 0: skip)")
+                    help="--mode hub with bypass and --full: utterances per relay timed afterwards "
+                         "with the bypass off (the window_300ms secondary field; 0: skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need (the window_300ms pass)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned as DIR/<name>.npy")
     ap.add_argument("--inflight", type=int, default=2,
                     help="--mode batch: batches in flight (2: next batch's STT overlaps the decode)")
     ap.add_argument("--cpu-smoke", action="store_true", help="tiny models on CPU (plumbing test)")
@@ -512,8 +649,11 @@ def main(argv=None) -> int:
     # transcript -> distinct prompt, so only the template text before the
     # transcript can hit the prefix cache), drawn up front for the warmup and
     # timed rounds; each stream's command count cycles through the mix
-    win_steps = args.window_steps if (args.mode == "hub" and args.bypass) else 0
-    n_per_stream = args.warmup + args.steps + win_steps
+    # the window pass's utterances are drawn either way (an utterance depends
+    # on its index in the whole draw); only --full runs them
+    win_drawn = args.window_steps if (args.mode == "hub" and args.bypass) else 0
+    win_steps = win_drawn if args.full else 0
+    n_per_stream = args.warmup + args.steps + win_drawn
     uniq = []
     if args.mode in ("closed", "hub"):
         counts = [mix[(ci + k) % len(mix)] for ci in range(B) for k in range(n_per_stream)]
@@ -575,6 +715,11 @@ def main(argv=None) -> int:
             return run_hub(n, record)
         return run_closed(n, record) if args.mode == "closed" else run_batches(n, record)
 
+    probe = None
+    if args.dump_outputs:
+        last_k = args.warmup + args.steps - 1
+        probe = EncoderProbe(stt, {u.text for u in mine} if args.mode == "batch" else
+                             {uniq[ci * n_per_stream + last_k].text for ci in range(B)}, args.seed)
     loop.run_until_complete(run(args.warmup, False))
     pdist.barrier(info)
     if dev.type == "cuda":
@@ -593,6 +738,8 @@ def main(argv=None) -> int:
     elapsed = pdist.max_over_ranks(info, time.perf_counter() - t0)
     if hub is not None:
         hub.processor.job_sink = None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, *last_step_outputs(all_jobs, probe), info.rank)
 
     if hub is not None:
         # commands each timed utterance actually published on loqa.voice.commands

@@ -226,14 +226,68 @@ def _run(cmd, timeout=600):
     return json.loads(lines[0])
 
 
-def test_bench_cpu_smoke_single():
-    out = _run([sys.executable, "bench.py", "--cpu-smoke", "--steps", "1", "--warmup", "0",
-                "--batch-per-gpu", "4"])
+def test_bench_cpu_smoke_single(tmp_path):
+    steps = 2
+    cmd = [sys.executable, "bench.py", "--cpu-smoke", "--steps", str(steps), "--warmup", "0",
+           "--batch-per-gpu", "4"]
+    dump = tmp_path / "out"
+    out = _run(cmd + ["--dump-outputs", str(dump)])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
               "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"):
         assert k in out
     assert out["n_gpus"] == 1 and out["queue_success_rate"] == 1.0
-    assert out["command_count_match_rate"] == 1.0
+    assert out["command_count_match_rate"] == 1.0 and out["steps"] == steps
+    # a plain run stops after the timed steps: the window pass is --full's
+    assert out["window_300ms"] is None
+    # --dump-outputs: the LAST timed step's results, one row per stream
+    got = {p.name: np.load(p) for p in dump.glob("*.npy")}
+    assert sorted(got) == ["commands.npy", "encoder_xkv.npy", "rms.npy", "stt_confidence.npy",
+                           "stt_text.npy"]
+    assert all(a.dtype in (np.float32, np.float64) and len(a) == 4 for a in got.values())
+    from loqa_hub_amd.engine.stt_engine import STTEngine, STTRequest
+    from loqa_hub_amd.llm.transcriber import to_transcription_result
+    from loqa_hub_amd.models.configs import whisper_config
+    from loqa_hub_amd.transport.relay_sim import relay_utterances
+    # the bench's draw: steps + window slots per relay; each relay's last timed utterance
+    last = [u[steps - 1] for u in relay_utterances(0, [1, 2, 3, 4], 4, steps + 4)]
+    cmds = got["commands.npy"]
+    assert cmds[:, 1].tolist() == [float(u.n_commands) for u in last]
+    assert (cmds[:, 0] == cmds[:, 1]).all() and (cmds[:, 2] == 1.0).all()
+    for row, rms, conf, u in zip(got["stt_text.npy"], got["rms.npy"], got["stt_confidence.npy"], last):
+        want = to_transcription_result(u.text)
+        assert row[0] == len(want.text)
+        assert "".join(chr(int(c)) for c in row[1:][row[1:] >= 0]) == want.text
+        assert conf == np.float32(want.confidence_estimate)
+        x = u.pcm.astype(np.float64) / 32767.0
+        assert abs(rms - np.sqrt((x * x).mean())) <= 1e-5 * rms
+    # the encoder's result: an engine of the same seed, each utterance alone.
+    # The K|V buffer is bf16: a row encoded in another batch may round one
+    # bf16 ulp (2^-8 relative) the other way
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    eng = STTEngine(whisper_config("test-whisper"), torch.device("cpu"), seed=0, max_batch=8)
+    probe = bench.EncoderProbe(eng, {u.text for u in last}, 0)
+    for u in last:
+        eng.transcribe([STTRequest(u.pcm, transcript=u.text)])
+    ref = np.stack([probe.samples[u.text] for u in last])
+    assert np.abs(ref).max() > 0 and len({r.tobytes() for r in ref}) == 4
+    np.testing.assert_allclose(got["encoder_xkv.npy"], ref, rtol=2.0 ** -7, atol=1e-3)
+    replies = [json.loads(ln) for ln in (dump / "llm_replies.jsonl").read_text().splitlines()]
+    for rep, u in zip(replies, last):
+        reply = json.loads(rep["llm_output"])
+        # a one-command utterance is parsed with the single-command schema
+        assert len(reply.get("commands", [reply])) == u.n_commands
+    # the same arguments again: the same inputs, the same arrays
+    dump2 = tmp_path / "again"
+    _run(cmd + ["--dump-outputs", str(dump2)])
+    for name, a in got.items():
+        b = np.load(dump2 / name)
+        if name in ("encoder_xkv.npy", "rms.npy"):
+            np.testing.assert_allclose(b, a, rtol=2.0 ** -7 if name[0] == "e" else 1e-6, atol=1e-3)
+        else:
+            assert np.array_equal(a, b), name
 
 
 def test_bench_cpu_smoke_dp2_gloo():
@@ -313,7 +367,7 @@ def test_bench_cpu_smoke_hub_mode():
     voice events) on the same pipeline."""
     out = _run([sys.executable, "bench.py", "--cpu-smoke", "--steps", "1",
                 "--warmup", "1", "--batch-per-gpu", "2", "--window-ms", "10",
-                "--window-steps", "1"])
+                "--window-steps", "1", "--full"])
     # hub mode + single-relay bypass are the defaults; the window_300ms pass
     # (bypass off) adds one utterance per relay after the timed step
     assert out["config"]["mode"] == "hub" and out["queue_success_rate"] == 1.0
