@@ -53,7 +53,8 @@ class FusedParams(ctypes.Structure):
 
 
 class GemmTileParams(ctypes.Structure):
-    """Mirror of ``GemmTileParams`` in csrc/kernels/gemm_tile.hip."""
+    """Mirror of ``GemmTileParams`` in csrc/kernels/gemm_tile.hip (``epi``: the
+    numbering of csrc/kernels/gemm_mfma.h, as ``ops.gemm._EPI``)."""
     _fields_ = [
         ("x", c_void_p), ("ldx", c_ll), ("w", c_void_p),
         ("M", c_int), ("N", c_int), ("K", c_int), ("S", c_int),
@@ -113,6 +114,7 @@ _KERNEL_SIGS = {
     "loqa_shuffle_weight": [c_void_p, c_void_p, c_int, c_int, c_void_p],
     "loqa_skinny_fused": [c_void_p, c_void_p],
     "loqa_gemm_tile": [c_void_p, c_void_p],
+    "loqa_gemm_tile_dims": [c_int, c_void_p, c_void_p],
     "loqa_gemm_sk": [c_void_p, c_void_p],
     "loqa_gemm_sk_dims": [c_int, c_void_p, c_void_p],
     "loqa_gemm_ws": [c_void_p, c_int, c_void_p],
