@@ -18,18 +18,18 @@ ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 KDIR = os.path.join(ROOT, "csrc", "kernels")
 
 LABELS = {
-    "SF<2, 1, 4, 4, 1, 1, 0, 0, 0>": "8B gate|up (SiLU, RMS prologue)",
-    "SF<2, 1, 4, 1, 2, 0, 0, 0, 0>": "8B down (+residual)",
-    "SF<2, 1, 4, 1, 3, 1, 0, 0, 0>": "8B qkv (RoPE + KV append, RMS)",
-    "SF<1, 1, 4, 1, 2, 0, 0, 0, 0>": "8B o (+residual)",
-    "SF<1, 1, 2, 1, 2, 0, 0, 0, 0>": "Whisper o / cross-o (+residual)",
-    "SF<2, 1, 2, 1, 4, 2, 0, 0, 0>": "Whisper fc1 (GELU, LN)",
-    "SF<2, 1, 2, 1, 2, 0, 0, 0, 0>": "Whisper fc2 (+residual)",
-    "SF<1, 1, 2, 1, 3, 2, 0, 0, 0>": "Whisper self qkv (LN, KV append)",
-    "SF<1, 1, 2, 1, 4, 2, 0, 0, 0>": "Whisper cross q (LN)",
-    "SF<2, 1, 4, 1, 1, 1, 0, 0, 0>": "70B shard gate|up",
-    "SF<2, 1, 4, 1, 4, 0, 0, 0, 0>": "70B shard o / down (partials)",
-    "SF<1, 1, 4, 1, 3, 1, 0, 0, 0>": "70B shard qkv",
+    "SF<2, 1, 4, 4, 1, 1, 0>": "8B gate|up (SiLU, RMS prologue)",
+    "SF<2, 1, 4, 1, 2, 0, 0>": "8B down (+residual)",
+    "SF<2, 1, 4, 1, 3, 1, 0>": "8B qkv (RoPE + KV append, RMS)",
+    "SF<1, 1, 4, 1, 2, 0, 0>": "8B o (+residual)",
+    "SF<1, 1, 2, 1, 2, 0, 0>": "Whisper o / cross-o (+residual)",
+    "SF<2, 1, 2, 1, 4, 2, 0>": "Whisper fc1 (GELU, LN)",
+    "SF<2, 1, 2, 1, 2, 0, 0>": "Whisper fc2 (+residual)",
+    "SF<1, 1, 2, 1, 3, 2, 0>": "Whisper self qkv (LN, KV append)",
+    "SF<1, 1, 2, 1, 4, 2, 0>": "Whisper cross q (LN)",
+    "SF<2, 1, 4, 1, 1, 1, 0>": "70B shard gate|up",
+    "SF<2, 1, 4, 1, 4, 0, 0>": "70B shard o / down (partials)",
+    "SF<1, 1, 4, 1, 3, 1, 0>": "70B shard qkv",
     "attn_decode_kernel<128, 0, 4, 2>": "Llama decode attention (D 128)",
     "attn_decode_kernel<64, 0, 4, 2>": "Whisper self / cross attention (D 64)",
 }

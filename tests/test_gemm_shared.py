@@ -41,6 +41,14 @@ def test_layout_tables_match_the_kernels():
     assert lib.loqa_gemm_tile_dims(len(ops.GEMM_TILE_LAYOUTS), ctypes.byref(bn), ctypes.byref(bm)) != 0
 
 
+def test_fused_params_mirror_has_the_kernels_size():
+    """_lib.FusedParams is gemm_skinny.hip's FusedParams restated by hand: hold
+    its size to the exported sizeof (host-only call, no GPU work)."""
+    if not _lib.available():
+        pytest.skip("native kernels library not built")
+    assert ctypes.sizeof(_lib.FusedParams) == _lib.kernels().loqa_skinny_fused_params_size()
+
+
 @pytest.fixture(scope="module")
 def inputs():
     dev = torch.device("cuda", 0)
