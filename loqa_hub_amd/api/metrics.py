@@ -48,6 +48,12 @@ class MetricsHandler:
         if pipe is not None:
             for k, v in pipe.llm.stats.items():
                 out.append(_line("loqa_llm_" + k, v))
+            lw = getattr(pipe.llm, "weights", None)
+            if hasattr(lw, "resident_bytes"):
+                # resident LLM weights and their projection dtype (HUB_LLM_WEIGHTS)
+                out.append(_line("loqa_llm_weight_bytes", lw.resident_bytes()))
+                out.append(_line("loqa_llm_weight_dtype", 1,
+                                 {"dtype": getattr(lw, "weight_dtype", "bf16")}))
             for k, v in pipe.stt.stats.items():
                 out.append(_line("loqa_stt_" + k, v))
         from ..utils.tracing import tracer

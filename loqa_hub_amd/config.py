@@ -199,6 +199,9 @@ class GPUConfig:
     kv_block: int = 16
     max_seq_len: int = 1024
     llm_backend: str = "gpu"          # gpu | ollama
+    # LLM projection / lm_head weights: bf16, or fp8 (e4m3 weight streams with
+    # per-row scales: half the bytes per decode step; one GPU, gpu backend)
+    llm_weights: str = "bf16"
     stt_backend: str = "gpu"          # gpu | http
     tts_backend: str = "gpu"          # gpu | http | none
     use_graphs: bool = True
@@ -303,6 +306,15 @@ class Config:
             raise ConfigError(f"invalid ARBITRATION_SCOPE: {self.arbitration.scope}")
         if self.gpu.tp < 1:
             raise ConfigError(f"HUB_TP must be >= 1: {self.gpu.tp}")
+        if self.gpu.llm_weights not in ("bf16", "fp8"):
+            raise ConfigError(f"invalid HUB_LLM_WEIGHTS (bf16 | fp8): {self.gpu.llm_weights}")
+        if self.gpu.llm_weights == "fp8":
+            if self.gpu.tp > 1:
+                raise ConfigError("HUB_LLM_WEIGHTS=fp8 needs HUB_TP=1 (no tensor-parallel fp8 "
+                                  f"shards): HUB_TP={self.gpu.tp}")
+            if self.gpu.llm_backend != "gpu":
+                raise ConfigError("HUB_LLM_WEIGHTS=fp8 needs HUB_LLM_BACKEND=gpu: "
+                                  f"{self.gpu.llm_backend}")
 
 
 def parse_relay_groups(s: str) -> dict:
@@ -393,6 +405,7 @@ def load(env=None) -> Config:
             kv_block=env_int(e, 16, "HUB_KV_BLOCK"),
             max_seq_len=env_int(e, 1024, "HUB_MAX_SEQ_LEN"),
             llm_backend=env_str(e, "gpu", "HUB_LLM_BACKEND"),
+            llm_weights=env_str(e, "bf16", "HUB_LLM_WEIGHTS").lower(),
             stt_backend=env_str(e, "gpu", "HUB_STT_BACKEND"),
             tts_backend=env_str(e, "gpu", "HUB_TTS_BACKEND"),
             use_graphs=env_bool(e, True, "HUB_USE_GRAPHS"),

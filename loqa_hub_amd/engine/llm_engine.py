@@ -78,18 +78,33 @@ class LLMEngine:
                  max_seq_len: int = 1024, block_size: int = 16, num_blocks: int | None = None,
                  tp: TPGroup | None = None, use_graphs: bool = True, prefill_chunk: int = 8192,
                  weights: LlamaWeights | None = None, fused_decode: bool = True,
-                 compact: bool = False, tokenizer=None):
+                 compact: bool = False, tokenizer=None, weight_dtype: str = "bf16"):
         self.cfg = cfg
         self.device = torch.device(device)
         if self.device.type == "cuda" and self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.tp = tp or TPGroup()
+        # "fp8": every projection and the lm_head as e4m3 weight streams (half
+        # the bytes per decode step; implies the compact single-copy layout)
+        if weight_dtype not in ("bf16", "fp8"):
+            raise ValueError(f"weight_dtype must be 'bf16' or 'fp8', got {weight_dtype!r}")
+        if weight_dtype == "fp8":
+            if self.tp.world > 1:
+                raise ValueError("weight_dtype='fp8' is single-GPU only (no tensor-parallel fp8 shards)")
+            if not fused_decode:
+                raise ValueError("weight_dtype='fp8' needs fused_decode=True (fp8 weights exist "
+                                 "only in the fused decode layout)")
+            if weights is not None and getattr(weights, "weight_dtype", "bf16") != "fp8":
+                raise ValueError("weight_dtype='fp8' but the given weights are bf16")
+        elif weights is not None:
+            weight_dtype = getattr(weights, "weight_dtype", "bf16")
+        self.weight_dtype = weight_dtype
         from ..utils.streams import decode_cap, init_pools
         init_pools(self.device)       # fixed stream -> hardware-queue placement
         self.max_wgs = decode_cap("LOQA_LLM_MAX_WGS")
         with ops.decode_cap(self.max_wgs):
             self.weights = weights or LlamaWeights(cfg, self.device, seed=seed, tp=self.tp,
-                                                   compact=compact)
+                                                   compact=compact, weight_dtype=weight_dtype)
         self.weights.max_wgs = self.max_wgs or ops.MAX_DECODE_WGS
         self.model = LlamaModel(self.weights)
         # a checkpoint's own tokenizer (tokenizer.HFTokenizer), else the

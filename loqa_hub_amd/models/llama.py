@@ -115,9 +115,15 @@ class TPGroup:
 
 class LlamaWeights:
     def __init__(self, cfg: LlamaConfig, device, dtype=torch.bfloat16, seed: int = 0,
-                 tp: TPGroup | None = None, compact: bool = False):
+                 tp: TPGroup | None = None, compact: bool = False, weight_dtype: str = "bf16"):
         tp = tp or TPGroup()
         self.cfg, self.tp = cfg, tp
+        # "fp8": the projections and the lm_head are e4m3 weight streams with a
+        # per-row scale (ops.Fp8Weight) - half the bytes read per decode step,
+        # half the resident weights. Implies ``compact``; the embedding table,
+        # the norms, the KV cache and cos_sin stay bf16 / f32.
+        self.weight_dtype = self._check_weight_dtype(weight_dtype, tp)
+        compact = compact or weight_dtype == "fp8"
         # compact: ONE copy of every projection, in the fused decode layout
         # (prefill then runs through the fused GEMMs in <= 64-token chunks).
         # Llama-3-70B bf16 (141 GB) fits one 288 GB MI355X this way, and a
@@ -176,15 +182,30 @@ class LlamaWeights:
                                     scaling=cfg.rope_scaling)
         self._finalize()
 
+    @staticmethod
+    def _check_weight_dtype(weight_dtype: str, tp: TPGroup) -> str:
+        if weight_dtype not in ("bf16", "fp8"):
+            raise ValueError(f"weight_dtype must be 'bf16' or 'fp8', got {weight_dtype!r}")
+        if weight_dtype == "fp8" and tp.world > 1:
+            raise ValueError("weight_dtype='fp8' is single-GPU only (no tensor-parallel fp8 shards)")
+        return weight_dtype
+
+    def _pack(self, w: torch.Tensor):
+        """A row-major projection -> its decode-GEMM operand: fragment-ordered
+        bf16, or (fp8) quantised per row, then fragment-ordered."""
+        if getattr(self, "weight_dtype", "bf16") == "fp8":
+            return ops.quantize_weight_fp8(w.contiguous())
+        return ops.shuffle_weight(w.contiguous())
+
     def _compact_layer(self, L: dict) -> dict:
+        # per projection: fold norm -> permute rows -> (quantise) -> shuffle
         from ..ops import reference as _ref
         dev = L["wqkv"].device
         pq = _ref.perm_rope_qkv(self.h, self.hkv, self.cfg.head_dim).to(dev)
         pg = _ref.perm_gate_up(self.f).to(dev)
-        return {"wqkv_f": ops.shuffle_weight(ops.fold_norm(L["wqkv"], L["attn_norm"])[pq].contiguous()),
-                "w_gate_up_f": ops.shuffle_weight(
-                    ops.fold_norm(L["w_gate_up"], L["mlp_norm"])[pg].contiguous()),
-                "wo": ops.shuffle_weight(L["wo"]), "w_down": ops.shuffle_weight(L["w_down"])}
+        return {"wqkv_f": self._pack(ops.fold_norm(L["wqkv"], L["attn_norm"])[pq]),
+                "w_gate_up_f": self._pack(ops.fold_norm(L["w_gate_up"], L["mlp_norm"])[pg]),
+                "wo": self._pack(L["wo"]), "w_down": self._pack(L["w_down"])}
 
     def _finalize(self) -> None:
         """Derived decode copies + split-K tuning (after the base tensors exist)."""
@@ -218,16 +239,20 @@ class LlamaWeights:
         pad = -w.shape[0] % 64
         if pad:
             w = torch.cat([w, torch.zeros(pad, w.shape[1], dtype=w.dtype, device=w.device)])
-        return ops.shuffle_weight(w.contiguous())
+        return self._pack(w)
 
     @classmethod
     def from_tensors(cls, cfg: LlamaConfig, device, *, embed, layers: list[dict], final_norm,
-                     lm_head=None, tp: TPGroup | None = None) -> "LlamaWeights":
+                     lm_head=None, tp: TPGroup | None = None,
+                     weight_dtype: str = "bf16") -> "LlamaWeights":
         """Weights from explicit tensors (checkpoint loaders): ``layers`` hold
         attn_norm / wqkv (q|k|v rows) / wo / mlp_norm / w_gate_up (gate|up rows)
-        / w_down. Unsharded tensors; ``tp`` > 1 shards them (Megatron split)."""
+        / w_down. Unsharded tensors; ``tp`` > 1 shards them (Megatron split).
+        ``weight_dtype`` "fp8": the compact fp8 layout, converted layer by layer
+        (``layers`` is emptied of its row-major projections as it goes)."""
         self = cls.__new__(cls)
         self.cfg, self.tp = cfg, TPGroup()
+        self.weight_dtype = cls._check_weight_dtype(weight_dtype, tp or TPGroup())
         self.h, self.hkv, self.f, self.v = cfg.n_heads, cfg.n_kv_heads, cfg.ffn_dim, cfg.vocab_size
         self.embed = embed
         self.layers = layers
@@ -238,6 +263,13 @@ class LlamaWeights:
         if tp is not None and tp.world > 1:
             self.decode_layers, self.lm_head_p = [], None
             return cls.shard(self, tp)
+        if weight_dtype == "fp8":
+            self.compact = True
+            self.decode_layers = []
+            for i, L in enumerate(layers):
+                self.decode_layers.append(self._compact_layer(L))
+                layers[i] = {"attn_norm": L["attn_norm"], "mlp_norm": L["mlp_norm"]}
+                L.clear()                 # drop the row-major copies now
         self._finalize()
         return self
 
@@ -284,6 +316,7 @@ class LlamaWeights:
         qs, ks = slice(r * self.h * D, (r + 1) * self.h * D), slice(r * self.hkv * D, (r + 1) * self.hkv * D)
         fs, vs = slice(r * self.f, (r + 1) * self.f), slice(r * self.v, (r + 1) * self.v)
         self.compact = False
+        self.weight_dtype = "bf16"
         self.embed = full.embed          # replicated (see __init__)
         self.layers = []
         for L in full.layers:
@@ -308,6 +341,29 @@ class LlamaWeights:
         for L in self.layers:
             n += sum(t.numel() for t in L.values())
         return n * 2
+
+    def resident_bytes(self) -> int:
+        """Bytes of every weight tensor this object keeps resident (each
+        storage once): embedding, norms, row-major and decode copies, fp8
+        streams with their scales, the lm_head copy."""
+        seen, total = set(), 0
+
+        def add(t):
+            nonlocal total
+            if isinstance(t, ops.Fp8Weight):
+                add(t.wp); add(t.scale)
+            elif isinstance(t, torch.Tensor):
+                key = t.untyped_storage().data_ptr()
+                if key not in seen:
+                    seen.add(key)
+                    total += t.untyped_storage().nbytes()
+        for t in (self.embed, getattr(self, "lm_head", None), getattr(self, "lm_head_p", None),
+                  self.final_norm):
+            add(t)
+        for L in list(self.layers) + list(getattr(self, "decode_layers", [])):
+            for t in L.values():
+                add(t)
+        return total
 
 
 # prompt passes on the hand-written GEMMs (ops.proj: split-K tiled / weight-
@@ -577,7 +633,8 @@ class LlamaModel:
         (pre-shuffled copy, rows padded to 16; f32 logits), not hipBLASLt."""
         w = self.w
         B = hidden.shape[0]
-        if (hidden.is_cuda and getattr(w, "lm_head_p", None) is not None
+        fp8 = isinstance(getattr(w, "lm_head_p", None), ops.Fp8Weight)   # the only lm_head copy
+        if ((hidden.is_cuda or fp8) and getattr(w, "lm_head_p", None) is not None
                 and B <= ops.MPADS[-1]):
             Mpad = ops.mpad_for(B)
             x = hidden

@@ -88,30 +88,36 @@ def llama_state_dict(w: LlamaWeights) -> dict[str, torch.Tensor]:
 
 
 def llama_from_state_dict(cfg: LlamaConfig, sd: dict[str, torch.Tensor], device,
-                          tp: TPGroup | None = None) -> LlamaWeights:
+                          tp: TPGroup | None = None, weight_dtype: str = "bf16") -> LlamaWeights:
+    """``weight_dtype`` "fp8": the checkpoint is served from e4m3 weight streams
+    (``LlamaWeights.from_tensors`` converts layer by layer; the per-projection
+    tensors leave ``sd`` here, so each row-major layer is freed once converted)."""
+    take = sd.pop if weight_dtype == "fp8" else sd.__getitem__
     layers = []
     for i in range(cfg.n_layers):
         p = f"model.layers.{i}."
         layers.append({
             "attn_norm": sd[p + "input_layernorm.weight"],
-            "wqkv": torch.cat([sd[p + "self_attn.q_proj.weight"], sd[p + "self_attn.k_proj.weight"],
-                               sd[p + "self_attn.v_proj.weight"]]).contiguous(),
-            "wo": sd[p + "self_attn.o_proj.weight"],
+            "wqkv": torch.cat([take(p + "self_attn.q_proj.weight"), take(p + "self_attn.k_proj.weight"),
+                               take(p + "self_attn.v_proj.weight")]).contiguous(),
+            "wo": take(p + "self_attn.o_proj.weight"),
             "mlp_norm": sd[p + "post_attention_layernorm.weight"],
-            "w_gate_up": torch.cat([sd[p + "mlp.gate_proj.weight"],
-                                    sd[p + "mlp.up_proj.weight"]]).contiguous(),
-            "w_down": sd[p + "mlp.down_proj.weight"]})
+            "w_gate_up": torch.cat([take(p + "mlp.gate_proj.weight"),
+                                    take(p + "mlp.up_proj.weight")]).contiguous(),
+            "w_down": take(p + "mlp.down_proj.weight")})
     return LlamaWeights.from_tensors(cfg, device, embed=sd["model.embed_tokens.weight"],
                                      layers=layers, final_norm=sd["model.norm.weight"],
-                                     lm_head=sd.get("lm_head.weight"), tp=tp)
+                                     lm_head=sd.get("lm_head.weight"), tp=tp,
+                                     weight_dtype=weight_dtype)
 
 
 def save_llama(w: LlamaWeights, path: str) -> None:
     write_safetensors(llama_state_dict(w), path)
 
 
-def load_llama(cfg: LlamaConfig, path: str, device, tp: TPGroup | None = None) -> LlamaWeights:
-    return llama_from_state_dict(cfg, read_safetensors(path, device), device, tp)
+def load_llama(cfg: LlamaConfig, path: str, device, tp: TPGroup | None = None,
+               weight_dtype: str = "bf16") -> LlamaWeights:
+    return llama_from_state_dict(cfg, read_safetensors(path, device), device, tp, weight_dtype)
 
 
 # -------------------------------------------------------------------- Whisper

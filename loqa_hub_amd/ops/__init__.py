@@ -422,15 +422,16 @@ def tune_skinny_splits(wp: torch.Tensor, mpads=MPADS, reps: int = 8) -> dict:
     if not _gpu(wp) or NO_TUNE:
         return {}
     out = {}
+    tag = _wtag(wp)
     for Mpad in mpads:
-        key = (N, K, Mpad)
+        key = (N, K, Mpad) + tag
         if key in _SPLITS:
             out[key] = _SPLITS[key]
             continue
         x = torch.randn(Mpad, K, device=wp.device, dtype=torch.bfloat16)
         best, best_t = 1, float("inf")
         for s in SPLIT_CANDIDATES:
-            if K % (s * 128):
+            if K % (s * (256 if tag else 128)):
                 continue
             t = graph_time(lambda: skinny_gemm(x, wp, s), reps)
             if t < best_t * 0.98:
@@ -472,7 +473,7 @@ def _fsplit_override(key: tuple) -> tuple[int, int, int] | None:
     """``LOQA_FSPLIT_OVERRIDE="silu:28672x4096:M16=2,2,1;..."`` pins the
     (split-K, rt, wr) of a fused GEMM shape (experiments / deployment pins)."""
     spec = os.environ.get("LOQA_FSPLIT_OVERRIDE", "")
-    name = f"{key[0]}:{key[1]}x{key[2]}:M{key[3]}"
+    name = f"{key[0]}:{key[1]}x{key[2]}:M{key[3]}" + "".join(f":{t}" for t in key[4:])
     for item in spec.split(";"):
         if "=" in item:
             k, v = item.split("=", 1)
@@ -557,7 +558,8 @@ def tune_fused_splits(key: tuple, run, K: int, reps: int = 8, rts=(2,), ncopies:
     any reduction; ``wr4`` adds the 4-waves-along-rows layout (S = 1 only). ``xl``: "no",
     "also" (add the x-through-LDS layouts, any split) or "only" (Mpad 128).
     Returns (split-K, rt, wr) or (split-K, rt, 4, 1) for an XL layout.
-    ``key`` = (mode, N, K, Mpad)."""
+    ``key`` = (mode, N, K, Mpad), with "fp8" appended for an fp8 weight stream
+    (a wave's k range is then a whole number of 64-wide k-step pairs)."""
     if key in _FSPLITS:
         return _FSPLITS[key]
     ov = _fsplit_override(key)
@@ -565,10 +567,11 @@ def tune_fused_splits(key: tuple, run, K: int, reps: int = 8, rts=(2,), ncopies:
         _FSPLITS[key] = ov
         return ov
     N = key[1]
+    kq = 64 if len(key) > 4 else 32      # k granule of one weight load
     cands = [] if xl == "only" else \
-        [(s, rt, 1) for rt in rts for s in SPLIT_CANDIDATES if K % (s * 128) == 0]
+        [(s, rt, 1) for rt in rts for s in SPLIT_CANDIDATES if K % (s * 4 * kq) == 0]
     if wr4 and xl != "only":
-        cands += [(1, rt, 4) for rt in rts if N % (64 * rt) == 0]
+        cands += [(1, rt, 4) for rt in rts if N % (64 * rt) == 0 and K % kq == 0]
     if xl != "no":
         cands += [(s, rt, 4, 1) for rt in (1, 2) for s in SPLIT_CANDIDATES
                   if K % (s * 128) == 0 and N % (64 * rt) == 0]
@@ -652,17 +655,17 @@ def graph_time(fn, reps: int = 8, trials: int = 3) -> float:
     return best
 
 
-def choose_splits(N: int, K: int, Mpad: int, target_wgs: int = 512) -> int:
+def choose_splits(N: int, K: int, Mpad: int, target_wgs: int = 512, tag: tuple = ()) -> int:
     """Split-K factor: the tuned value if available, else enough splits for
-    >= ~2 workgroups per CU (256 CUs)."""
-    tuned = _SPLITS.get((N, K, Mpad))
+    >= ~2 workgroups per CU (256 CUs). ``tag`` = ("fp8",) for an fp8 weight."""
+    tuned = _SPLITS.get((N, K, Mpad) + tag)
     if tuned is not None:
         return tuned
     rt = 2 if Mpad <= 32 else 4
     tiles = max(1, N // (16 * rt))
     best = 1
     for s in SPLIT_CANDIDATES:
-        if K % (s * 128) != 0:
+        if K % (s * (256 if tag else 128)) != 0:
             continue
         best = s
         if tiles * s >= target_wgs:
@@ -697,20 +700,73 @@ def shuffle_weight(w: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def skinny_gemm(x: torch.Tensor, wp: torch.Tensor, splits: int | None = None,
+class Fp8Weight:
+    """A decode GEMM weight as an fp8 (OCP e4m3fn) stream: ``wp`` uint8
+    [N/16, K/64, 64, 16] in the kernels' fp8 fragment order (``ref.shuffle_fp8``)
+    and ``scale`` f32 [N], one per row (in the row order of ``wp``). Stands in
+    for a shuffled bf16 weight wherever the decode GEMMs take one: ``shape`` is
+    the shape of that bf16 tensor, so ``shape[0] * 16`` / ``shape[1] * 32``
+    give N and K as they do for it."""
+
+    def __init__(self, wp: torch.Tensor, scale: torch.Tensor, N: int, K: int):
+        assert wp.dtype == torch.uint8 and wp.shape == (N // 16, K // 64, 64, 16)
+        assert scale.dtype == torch.float32 and scale.shape == (N,)
+        self.wp, self.scale, self.N, self.K = wp, scale, N, K
+
+    shape = property(lambda self: (self.N // 16, self.K // 32, 64, 8))
+    device = property(lambda self: self.wp.device)
+    is_cuda = property(lambda self: self.wp.is_cuda)
+    nbytes = property(lambda self: self.wp.numel() + 4 * self.scale.numel())
+
+    def numel(self) -> int:
+        return self.wp.numel()
+
+    def element_size(self) -> int:
+        return 1
+
+    def clone(self) -> "Fp8Weight":
+        return Fp8Weight(self.wp.clone(), self.scale.clone(), self.N, self.K)
+
+    def to(self, device) -> "Fp8Weight":
+        return Fp8Weight(self.wp.to(device), self.scale.to(device), self.N, self.K)
+
+
+def _wtag(wp) -> tuple:
+    """Suffix of the tuning-cache keys of a weight: () for bf16 (the keys are
+    what they always were), ("fp8",) for an fp8 stream."""
+    return ("fp8",) if isinstance(wp, Fp8Weight) else ()
+
+
+def quantize_weight_fp8(w: torch.Tensor) -> Fp8Weight:
+    """[N, K] bf16 (rows already norm-folded and permuted) -> ``Fp8Weight``:
+    per-row scale amax / 448 (1 for an all-zero row, whose outputs are then
+    exactly 0), e4m3fn bytes in fragment order. Load time only."""
+    N, K = w.shape
+    assert N % 16 == 0 and K % 64 == 0, "fp8 weights need N % 16 == 0 and K % 64 == 0"
+    q, scale = ref.quantize_fp8_rows(w)
+    return Fp8Weight(ref.shuffle_fp8(q.view(torch.uint8)), scale.contiguous(), N, K)
+
+
+def skinny_gemm(x: torch.Tensor, wp, splits: int | None = None,
                 max_wgs: int = 0) -> torch.Tensor:
     """x [Mpad, K] bf16 (Mpad in 16/32/64/128, padded rows finite) @ W^T with W
-    given pre-shuffled (``shuffle_weight``) -> split-K partial slabs
-    [S, Mpad, N] f32 (sum over S = x @ W^T)."""
+    given pre-shuffled (``shuffle_weight``, or an ``Fp8Weight``) -> split-K
+    partial slabs [S, Mpad, N] f32 (sum over S = x @ W^T)."""
     Mpad, K = x.shape
     N = wp.shape[0] * 16
     assert wp.shape[1] * 32 == K, "weight/activation K mismatch"
-    S = splits or choose_splits(N, K, Mpad)
+    S = splits or choose_splits(N, K, Mpad, tag=_wtag(wp))
     if not _gpu(x):
         return ref.skinny_gemm(x, wp, S)
     assert Mpad in MPADS and x.dtype == torch.bfloat16 and x.stride(1) == 1
-    _bf16_contig(wp, "wp")
     part = torch.empty(S, Mpad, N, dtype=torch.float32, device=x.device)
+    if isinstance(wp, Fp8Weight):
+        assert wp.is_cuda and wp.wp.is_contiguous() and wp.scale.is_contiguous()
+        check(kernels().loqa_skinny_gemm_fp8(ptr(x), x.stride(0), ptr(wp.wp), ptr(wp.scale),
+                                             ptr(part), Mpad, N, K, S, max_wgs, stream_ptr(x)),
+              "skinny_gemm_fp8")
+        return part
+    _bf16_contig(wp, "wp")
     check(kernels().loqa_skinny_gemm(ptr(x), x.stride(0), ptr(wp), ptr(part), Mpad, N, K, S,
                                      max_wgs, stream_ptr(x)), "skinny_gemm")
     return part
@@ -1135,7 +1191,7 @@ def tune_fused(wp, mode: str, *, mpads=(16, 32, 64, 128), norm=None, act: str = 
     for Mpad in mpads:
         if Mpad == 128 and not xl_on:
             continue
-        key = (mode, N, K, Mpad)
+        key = (mode, N, K, Mpad) + _wtag(w)
         if key in _FSPLITS:
             continue
         x = torch.randn(Mpad, K, **bf)
@@ -1238,8 +1294,9 @@ def skinny_fused(x: torch.Tensor, wp, mode: str, scratch: FusedScratch, *,
     Mpad, K = x.shape
     N = wp.shape[0] * 16
     nrm = _NORMS[norm]
-    tuned = _FSPLITS.get((mode, N, K, Mpad))
-    S = splits or (tuned[0] if tuned else choose_splits(N, K, Mpad))
+    fp8 = isinstance(wp, Fp8Weight)
+    tuned = _FSPLITS.get((mode, N, K, Mpad) + _wtag(wp))
+    S = splits or (tuned[0] if tuned else choose_splits(N, K, Mpad, tag=_wtag(wp)))
     rt = rt or (tuned[1] if tuned else (1 if Mpad == 128 else 2))
     if xl is None:
         xl = tuned[3] if (tuned and not splits and len(tuned) > 3) else int(Mpad == 128)
@@ -1270,6 +1327,11 @@ def skinny_fused(x: torch.Tensor, wp, mode: str, scratch: FusedScratch, *,
     assert ntiles <= scratch.counters.numel() and ntiles * Mpad <= scratch.rowsq.numel()
     if nrm == 2:
         assert colsum is not None and colsum.numel() == N
+    if fp8:
+        assert nrm != 2, "fp8 weights: no LayerNorm prologue"
+        assert wp.is_cuda and wp.wp.is_contiguous() and wp.scale.is_contiguous()
+    else:
+        _bf16_contig(wp, "wp")
     if bias is not None:
         assert bias.dtype == torch.float32 and bias.numel() == N and bias.is_contiguous()
     if mode == "act":
@@ -1283,8 +1345,10 @@ def skinny_fused(x: torch.Tensor, wp, mode: str, scratch: FusedScratch, *,
     part = torch.empty(S, Mpad, N, dtype=torch.float32, device=x.device) if S > 1 else None
     blk = k_cache.shape[2] if k_cache is not None else 0
     p = FusedParams()
-    p.x, p.ldx, p.Wp, p.part, p.counters = ptr(x), x.stride(0), ptr(wp), ptr(part), \
-        ptr(scratch.counters)
+    p.x, p.ldx, p.Wp, p.part, p.counters = ptr(x), x.stride(0), ptr(wp.wp if fp8 else wp), \
+        ptr(part), ptr(scratch.counters)
+    if fp8:
+        p.wdtype, p.wscale = 1, ptr(wp.scale)
     p.Mpad, p.N, p.K, p.S, p.mode, p.norm = Mpad, N, K, S, m, nrm
     if nrm:
         p.rowsq_in, p.rowsum_in = ptr(scratch.rowsq), ptr(scratch.rowsum)

@@ -25,7 +25,7 @@ c_ll = ctypes.c_longlong
 c_float = ctypes.c_float
 
 class FusedParams(ctypes.Structure):
-    """Mirror of ``FusedParams`` in csrc/kernels/gemm_skinny.hip."""
+    """Mirror of ``FusedParams`` in csrc/kernels/gemm_skinny.h."""
     _fields_ = [
         ("x", c_void_p), ("ldx", c_ll), ("Wp", c_void_p), ("part", c_void_p),
         ("counters", c_void_p),
@@ -40,6 +40,7 @@ class FusedParams(ctypes.Structure):
         ("vc", c_void_p), ("slots", c_void_p),
         ("H", c_int), ("Hkv", c_int), ("D", c_int), ("blk", c_int),
         ("rt", c_int), ("wr", c_int), ("xl", c_int),
+        ("wdtype", c_int), ("wscale", c_void_p),
     ]
 
 
@@ -102,6 +103,8 @@ _KERNEL_SIGS = {
                        c_void_p],
     "loqa_skinny_gemm": [c_void_p, c_ll, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                          c_void_p],
+    "loqa_skinny_gemm_fp8": [c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                             c_int, c_int, c_void_p],
     "loqa_shuffle_weight": [c_void_p, c_void_p, c_int, c_int, c_void_p],
     "loqa_skinny_fused": [c_void_p, c_void_p],
     "loqa_skinny_fused_params_size": [],

@@ -286,7 +286,44 @@ def shuffle_weight(w):
         N // 16, K // 32, 64, 8)
 
 
+FP8_MAX = 448.0   # largest finite e4m3fn value
+
+
+def quantize_fp8_rows(w):
+    """Per-row e4m3fn quantisation of w [N, K]: (q float8_e4m3fn [N, K], scale
+    f32 [N]) with scale = amax(|row|) / 448 (1 for an all-zero row) and
+    w ~ q * scale. Clamped before the cast: torch's cast does not saturate."""
+    wf = w.float()
+    amax = wf.abs().amax(1)
+    scale = torch.where(amax > 0, amax / FP8_MAX, torch.ones_like(amax))
+    q = (wf / scale[:, None]).clamp(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn)
+    return q, scale
+
+
+def shuffle_fp8(q):
+    """e4m3 bytes [N, K] (uint8) -> fragment order [N/16, K/64, 64, 16]: lane l
+    holds row (l & 15); bytes 0-7 the 8 k values at offset 8 * (l >> 4) of
+    k-step 2j, bytes 8-15 the same of k-step 2j + 1."""
+    N, K = q.shape
+    return q.reshape(N // 16, 16, K // 64, 2, 4, 8).permute(0, 2, 4, 1, 3, 5).contiguous().reshape(
+        N // 16, K // 64, 64, 16)
+
+
+def unshuffle_fp8(wp):
+    T, KP = wp.shape[:2]
+    return wp.reshape(T, KP, 4, 16, 2, 8).permute(0, 3, 1, 4, 2, 5).reshape(T * 16, KP * 64)
+
+
+def dequant_fp8(weight):
+    """f32 [N, K] = e4m3 * scale of an fp8 weight container (``ops.Fp8Weight``:
+    ``wp`` uint8 in fragment order, ``scale`` f32 [N])."""
+    q = unshuffle_fp8(weight.wp).contiguous().view(torch.float8_e4m3fn)
+    return q.float() * weight.scale.float()[:, None]
+
+
 def unshuffle_weight(wp):
+    if hasattr(wp, "scale"):      # fp8 container: the dequantised rows (f32)
+        return dequant_fp8(wp)
     T, KS = wp.shape[:2]
     return wp.reshape(T, KS, 4, 16, 8).permute(0, 3, 1, 2, 4).reshape(T * 16, KS * 32)
 

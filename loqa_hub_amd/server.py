@@ -108,15 +108,18 @@ def build_gpu_processor(cfg: Config, nats, device: str = "cuda:0", tts=None, *, 
     if g.stt_checkpoint or (g.llm_checkpoint and llm is None):
         from .models import loader
         sw = loader.load_whisper(scfg, g.stt_checkpoint, device) if g.stt_checkpoint else None
-        lw = loader.load_llama(lcfg, g.llm_checkpoint, device) if (g.llm_checkpoint and llm is None) \
-            else None
+        lw = loader.load_llama(lcfg, g.llm_checkpoint, device, weight_dtype=g.llm_weights) \
+            if (g.llm_checkpoint and llm is None) else None
     stt = STTEngine(scfg, device, seed=g.seed, max_batch=g.max_batch, use_graphs=g.use_graphs,
                     weights=sw, tokenizer=g.tokenizer("stt", scfg.vocab_size),
                     language=cfg.stt.language)
     if llm is None:
         llm = LLMEngine(lcfg, device, seed=g.seed, max_seqs=g.max_batch, weights=lw,
                         max_seq_len=g.max_seq_len, block_size=g.kv_block, use_graphs=g.use_graphs,
-                        tokenizer=g.tokenizer("llm", lcfg.vocab_size))
+                        tokenizer=g.tokenizer("llm", lcfg.vocab_size), weight_dtype=g.llm_weights)
+    elif g.llm_weights != getattr(llm, "weight_dtype", "bf16"):
+        raise ValueError(f"HUB_LLM_WEIGHTS={g.llm_weights} but the prebuilt LLM engine holds "
+                         f"{getattr(llm, 'weight_dtype', 'bf16')} weights")
     if tts == "auto":
         tts = build_tts(cfg, device)
     pipe = VoicePipeline(stt, llm, nats)

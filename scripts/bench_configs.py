@@ -131,7 +131,7 @@ def config_2_or_5(cfg_id: int, args, dev, nats, tp_info=None) -> dict:
     else:
         # 70B at TP=1: one weight copy in the fused decode layout (141 GB)
         llm = LLMEngine(llama_config(llm_name), dev, seed=0, max_seqs=8, max_seq_len=1024,
-                        compact=llm_name == "llama3-70b")
+                        compact=llm_name == "llama3-70b", weight_dtype=args.weights)
     pipe = VoicePipeline(stt, llm, nats, min_response_tokens=8, max_batch=8)
     pipe.warmup()
     tts = None
@@ -158,6 +158,9 @@ def config_2_or_5(cfg_id: int, args, dev, nats, tp_info=None) -> dict:
     out = {
         "config": cfg_id, "model": f"{stt_name} + {llm_name}" + (" + vits-ljs" if tts else ""),
         "n_gpus": tp, "tp": tp, "streams": streams, "utterances": len(jobs), "dtype": "bf16",
+        "llm_weights": args.weights,
+        "llm_weight_bytes": (llm.weights.resident_bytes()
+                             if hasattr(getattr(llm, "weights", None), "resident_bytes") else None),
         "share_gpu": bool(args.share_gpu),
         "utterances_per_s": round(len(jobs) / wall, 3),
         "latency_ms_p50": round(float(np.median(lat)), 1),
@@ -180,7 +183,8 @@ def config_2_or_5(cfg_id: int, args, dev, nats, tp_info=None) -> dict:
                                                / ((llm.stats["decode_s"] - s0["decode_s"]) / steps * 1e3), 2)),
         "command_count_match": float(np.mean([j.n_commands == j.n_expected for j in jobs])),
         "init_s": round(init_s, 1),
-        "fused_gemm_tuning": {f"{k[0]}:{k[1]}x{k[2]}:M{k[3]}": list(v) for k, v in ops._FSPLITS.items()},
+        "fused_gemm_tuning": {f"{k[0]}:{k[1]}x{k[2]}:M{k[3]}" + "".join(f":{t}" for t in k[4:]): list(v)
+                              for k, v in ops._FSPLITS.items()},
         "data": "synthetic speech-like PCM16 + random-init weights (teacher-forced STT)",
     }
     if speech:
@@ -357,7 +361,12 @@ def main() -> int:
                     help="TP ranks share cuda:0 (spawned here when not under torchrun)")
     ap.add_argument("--compact", action="store_true",
                     help="TP: single-copy fused weights (needed when ranks share a GPU)")
+    ap.add_argument("--weights", choices=["bf16", "fp8"], default="bf16",
+                    help="configs 2 / 5, --tp 1: LLM projection weights (fp8: e4m3 weight streams, "
+                         "a secondary figure, never the headline)")
     args = ap.parse_args()
+    if args.weights == "fp8" and args.tp > 1:
+        ap.error("--weights fp8 is single-GPU only (--tp 1)")
     if args.tp > 1:
         if args.config != [5]:
             ap.error("--tp applies to --config 5 only")
