@@ -331,6 +331,12 @@ extern "C" int loqa_pcm16_f32_pad(const void* pcm, float* out, const long long* 
 // GPU); each workgroup folds its best (value, index) into one 64-bit atomicMax
 // of (order-preserving float key << 32 | ~index) - ties resolve to the lowest
 // index like torch.argmax. out_idx[b] = argmax over allowed tokens (or -1).
+// token_ids (optional, int32 [V]): the columns are a gathered subset of the
+// vocabulary (the compact sampling head) and out_idx[b] = token_ids[column];
+// the record keeps the column, so with ascending ids a tie still goes to the
+// lowest token id. A row that fits one chunk (V <= ARG_CHUNK) is one
+// workgroup, which writes out_idx[b] itself: no atomic, no zeroed workspace,
+// no unpack launch.
 #define ARG_CHUNK 8192
 #define ARG_THREADS 256
 
@@ -340,10 +346,18 @@ __device__ __forceinline__ unsigned long long argpack(float v, int idx) {
   return ((unsigned long long)key << 32) | (0xFFFFFFFFu - (uint32_t)idx);
 }
 
-template <bool BF16>
+__device__ __forceinline__ int argunpack(unsigned long long p, const int* __restrict__ token_ids) {
+  if (!p) return -1;
+  const int col = (int)(0xFFFFFFFFu - (uint32_t)(p & 0xFFFFFFFFull));
+  return token_ids ? token_ids[col] : col;
+}
+
+// SINGLE: gridDim.x == 1 (V <= ARG_CHUNK); the workgroup writes out_idx[b]
+template <bool BF16, bool SINGLE>
 __global__ __launch_bounds__(ARG_THREADS) void masked_argmax_kernel(
     const void* __restrict__ logits, long long ld, int V, const uint32_t* __restrict__ mask,
-    const int* __restrict__ mask_rows, int W, unsigned long long* __restrict__ packed) {
+    const int* __restrict__ mask_rows, int W, unsigned long long* __restrict__ packed,
+    const int* __restrict__ token_ids, int* __restrict__ out_idx) {
   __shared__ unsigned long long sbest[ARG_THREADS / 64];
   const int b = blockIdx.y;
   const int v_begin = blockIdx.x * ARG_CHUNK;
@@ -391,38 +405,54 @@ __global__ __launch_bounds__(ARG_THREADS) void masked_argmax_kernel(
   __syncthreads();
   if (threadIdx.x == 0) {
     for (int i = 1; i < ARG_THREADS / 64; ++i) best = max(best, sbest[i]);
-    if (best) atomicMax(packed + b, best);
+    if (SINGLE)
+      out_idx[b] = argunpack(best, token_ids);
+    else if (best)
+      atomicMax(packed + b, best);
   }
 }
 
 __global__ void argmax_unpack_kernel(const unsigned long long* __restrict__ packed, int B,
-                                     int* __restrict__ out_idx) {
+                                     const int* __restrict__ token_ids, int* __restrict__ out_idx) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b < B) {
-    const unsigned long long p = packed[b];
-    out_idx[b] = p ? (int)(0xFFFFFFFFu - (uint32_t)(p & 0xFFFFFFFFull)) : -1;
-  }
+  if (b < B) out_idx[b] = argunpack(packed[b], token_ids);
 }
 
-// workspace: >= B * 8 bytes (device)
+template <bool SINGLE>
+static void launch_masked_argmax(int is_bf16, dim3 grid, hipStream_t s, const void* logits,
+                                 long long ld, int V, const uint32_t* mask, const int* mask_rows,
+                                 int W, unsigned long long* packed, const int* token_ids,
+                                 int* out_idx) {
+  if (is_bf16)
+    hipLaunchKernelGGL((masked_argmax_kernel<true, SINGLE>), grid, dim3(ARG_THREADS), 0, s, logits,
+                       ld, V, mask, mask_rows, W, packed, token_ids, out_idx);
+  else
+    hipLaunchKernelGGL((masked_argmax_kernel<false, SINGLE>), grid, dim3(ARG_THREADS), 0, s, logits,
+                       ld, V, mask, mask_rows, W, packed, token_ids, out_idx);
+}
+
+// workspace: >= B * 8 bytes (device); only read when V > ARG_CHUNK.
+// token_ids: null, or int32 [V] (see above)
 extern "C" int loqa_masked_argmax(const void* logits, int is_bf16, long long ld, int B, int V,
                                   const uint32_t* mask, const int* mask_rows, int W, int* out_idx,
-                                  void* workspace, hipStream_t s) {
+                                  void* workspace, const int* token_ids, hipStream_t s) {
   if (B <= 0) return 0;
-  if ((mask && W * 32 < V) || !workspace) return (int)hipErrorInvalidValue;
+  if (V <= 0 || (mask && W * 32 < V) || !out_idx) return (int)hipErrorInvalidValue;
+  if (V <= ARG_CHUNK) {
+    launch_masked_argmax<true>(is_bf16, dim3(1, B), s, logits, ld, V, mask, mask_rows, W, nullptr,
+                               token_ids, out_idx);
+    return (int)hipGetLastError();
+  }
+  if (!workspace) return (int)hipErrorInvalidValue;
   unsigned long long* packed = (unsigned long long*)workspace;
   hipError_t e = hipMemsetAsync(packed, 0, sizeof(unsigned long long) * B, s);
   if (e != hipSuccess) return (int)e;
-  dim3 grid((V + ARG_CHUNK - 1) / ARG_CHUNK, B);
-  if (is_bf16)
-    hipLaunchKernelGGL(masked_argmax_kernel<true>, grid, dim3(ARG_THREADS), 0, s, logits, ld, V, mask,
-                       mask_rows, W, packed);
-  else
-    hipLaunchKernelGGL(masked_argmax_kernel<false>, grid, dim3(ARG_THREADS), 0, s, logits, ld, V,
-                       mask, mask_rows, W, packed);
+  launch_masked_argmax<false>(is_bf16, dim3((V + ARG_CHUNK - 1) / ARG_CHUNK, B), s, logits, ld, V,
+                              mask, mask_rows, W, packed, token_ids, out_idx);
   e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(argmax_unpack_kernel, dim3((B + 63) / 64), dim3(64), 0, s, packed, B, out_idx);
+  hipLaunchKernelGGL(argmax_unpack_kernel, dim3((B + 63) / 64), dim3(64), 0, s, packed, B, token_ids,
+                     out_idx);
   return (int)hipGetLastError();
 }
 

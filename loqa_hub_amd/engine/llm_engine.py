@@ -78,7 +78,8 @@ class LLMEngine:
                  max_seq_len: int = 1024, block_size: int = 16, num_blocks: int | None = None,
                  tp: TPGroup | None = None, use_graphs: bool = True, prefill_chunk: int = 8192,
                  weights: LlamaWeights | None = None, fused_decode: bool = True,
-                 compact: bool = False, tokenizer=None, weight_dtype: str = "bf16"):
+                 compact: bool = False, tokenizer=None, weight_dtype: str = "bf16",
+                 compact_head: str | None = None):
         self.cfg = cfg
         self.device = torch.device(device)
         if self.device.type == "cuda" and self.device.index is None:
@@ -115,6 +116,16 @@ class LLMEngine:
         self.grammar.trie(INTENTS)
         self.grammar.trie(["true", "false"])
         self.masks = self.grammar.mask_table(self.device)
+        self._n_mask_rows = self.masks.shape[0]
+        # compact sampling head ("auto" | "0" | "1", HUB_LLM_COMPACT_HEAD):
+        # built here, before any graph is captured
+        mode = (compact_head if compact_head is not None
+                else os.environ.get("HUB_LLM_COMPACT_HEAD", "auto")).strip().lower()
+        if mode not in ("auto", "0", "1"):
+            raise ValueError(f"HUB_LLM_COMPACT_HEAD must be auto, 0 or 1, got {mode!r}")
+        self.head = None
+        self.cmasks = None
+        self._init_compact_head(mode)
         self.max_seqs, self.max_seq_len = max_seqs, max_seq_len
         self.block_size = block_size
         self.max_blocks = (max_seq_len + block_size - 1) // block_size
@@ -248,18 +259,118 @@ class LLMEngine:
                 out[k] = t.to(self.device, non_blocking=True)
         return out
 
+    # ---------------------------------------------------- compact sampling head
+    # "auto" uses the compact head while it is at most this share of the
+    # vocabulary (padded rows). Measured on the Llama-3-8B step (docs/PERF.md
+    # "Compact sampling head"): 46 us saved at 75 %, 12 times the spread of
+    # repeated runs; at 100 % the saving is inside that spread
+    COMPACT_HEAD_MAX_SHARE = 0.75
+    MASK_ROWS_SPARE = 64      # compact mask rows kept free for later tries
+
+    @staticmethod
+    def compact_ids(rows: list[torch.Tensor]) -> tuple[torch.Tensor, torch.Tensor]:
+        """(ids, allowed) of mask rows ``rows`` (bool [V] each): ``allowed`` the
+        union of the rows, ``ids`` its token ids ascending as int32, padded to
+        a multiple of 16 with a repeat of the last id."""
+        allowed = torch.stack(rows).any(0)
+        ids = allowed.nonzero()[:, 0].to(torch.int32)
+        pad = -ids.numel() % 16
+        if pad and ids.numel():
+            ids = torch.cat([ids, ids[-1:].expand(pad)])
+        return ids, allowed
+
+    @staticmethod
+    def compact_mask(rows: list[torch.Tensor], ids: torch.Tensor, n: int) -> torch.Tensor:
+        """Packed compact mask [len(rows), ceil(len(ids) / 32)]: bit j of row r
+        = bit ``ids[j]`` of the full row r for the ``n`` real entries of
+        ``ids``; the padding's bits stay 0."""
+        from ..ops.reference import pack_mask
+        bits = torch.stack(rows)[:, ids.long()]
+        bits[:, n:] = False
+        return pack_mask(bits)
+
+    def _init_compact_head(self, mode: str) -> None:
+        """Take the lm_head rows the mask table can select (the table is built
+        once, here at start-up, and a token no row allows can never be
+        sampled) into a compact head; constrained sampling then streams those
+        rows only. The full head stays for everything else."""
+        if mode == "0" or self.tp.world > 1 or getattr(self.weights, "lm_head_p", None) is None:
+            if mode == "1" and self.tp.world > 1:
+                log.info("compact sampling head: off (tensor parallel keeps the vocab-parallel head)")
+            return
+        rows = self.grammar._rows
+        ids, allowed = self.compact_ids(rows)
+        n = int(allowed.sum())
+        V = self.weights.v
+        if n == 0:
+            return
+        n64, v64 = -(-ids.numel() // 64) * 64, -(-V // 64) * 64
+        if mode == "auto" and not (n64 < v64 and n64 <= self.COMPACT_HEAD_MAX_SHARE * v64):
+            return
+        self.head = self.weights.compact_head(ids.to(self.device))
+        cm = self.compact_mask(rows, ids, n)
+        self.cmasks = torch.zeros(len(rows) + self.MASK_ROWS_SPARE, cm.shape[1], dtype=torch.int32,
+                                  device=self.device)
+        self.cmasks[:len(rows)] = cm.to(self.device)
+        self._head_allowed, self._head_ids, self._head_n = allowed, ids, n
+        log.info("compact sampling head: %d of %d tokens (%d rows)", n, V, ids.numel())
+
+    def _sync_grammar(self, schema: list) -> None:
+        """Bring the mask tables up to a request's schema before its first
+        step. A ``GrammarTables.trie()`` after start-up adds mask rows: rows
+        whose tokens all lie inside the compact head are appended to the
+        compact table in place (captured graphs hold that buffer); a row with
+        a token outside it ends the compact head - the captured graphs are
+        dropped and sampling goes back to the full head. Correct, not fast."""
+        from .grammar import Choice
+        for s in schema:
+            if isinstance(s, Choice):
+                self.grammar.trie(s.options)
+        rows = self.grammar._rows
+        n0, n1 = self._n_mask_rows, len(rows)
+        if n1 == n0:
+            return
+        new = rows[n0:n1]
+        self._n_mask_rows = n1
+        inside = self.head is not None and n1 <= self.cmasks.shape[0] and \
+            not any(bool((r & ~self._head_allowed).any()) for r in new)
+        if inside:
+            self.cmasks[n0:n1] = self.compact_mask(new, self._head_ids, self._head_n).to(self.device)
+            self.masks = self.grammar.mask_table(self.device)
+            return
+        # the full table is a new tensor (and the compact head may be over):
+        # nothing captured may be replayed
+        if self._pl is not None:
+            self._pl.drain()
+        if self.is_gpu:
+            torch.cuda.synchronize(self.device)
+        if self.head is not None:
+            log.warning("compact sampling head: off - a grammar row added after start-up allows "
+                        "a token outside it; sampling from the full lm_head from here on")
+            self.head, self.cmasks = None, None
+            self.weights.lm_head_c = None
+        self._graphs.clear()
+        self._graphs_frozen = False
+        self._local_mask = None
+        self.masks = self.grammar.mask_table(self.device)
+
     # ------------------------------------------------------------ forward
     def _forward_sample(self, meta: StepMeta, mask_rows: torch.Tensor) -> torch.Tensor:
+        head = self.head
         if meta.decode:
             if self.fused_decode and meta.tokens.numel() <= 64:
                 logits = self.model.forward_decode_fused(meta, self.kv.k, self.kv.v, self.attn_ws,
-                                                         self.scratch, self.attn_split_keys)
+                                                         self.scratch, self.attn_split_keys, head=head)
             else:
-                logits = self.model.forward_decode(meta, self.kv.k, self.kv.v, self.attn_ws)
+                logits = self.model.forward_decode(meta, self.kv.k, self.kv.v, self.attn_ws,
+                                                   head=head)
             logits = logits[: mask_rows.numel()]
         else:
             hid = self.model.forward(meta, self.kv.k, self.kv.v, self.attn_ws)
-            logits = self.model.logits(hid)
+            logits = self.model.logits(hid, head=head)
+        if head is not None:
+            # columns are the head's tokens: compact mask, result mapped to token ids
+            return ops.masked_argmax(logits, self.cmasks, mask_rows, token_ids=head.ids)
         if self.tp.world == 1:
             return ops.masked_argmax(logits, self.masks, mask_rows)
         return self._tp_argmax(logits, mask_rows)
@@ -429,6 +540,7 @@ class LLMEngine:
     def submit(self, req: GenRequest) -> GenRequest:
         req.seq_id = self._next_id
         self._next_id += 1
+        self._sync_grammar(req.schema)
         req.grammar = GrammarState(self.grammar, req.schema)
         start = req.grammar.start()
         req.feed = list(req.prompt) + start

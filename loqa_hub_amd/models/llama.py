@@ -336,6 +336,13 @@ class LlamaWeights:
         self._finalize()
         return self
 
+    def compact_head(self, ids: torch.Tensor) -> "CompactHead":
+        """The compact sampling head over token ids ``ids`` (ascending): the
+        rows ``ids`` of the decode lm_head copy, kept on this object (counted
+        by ``resident_bytes``). The full ``lm_head_p`` stays."""
+        self.lm_head_c = CompactHead(self.lm_head_p, ids)
+        return self.lm_head_c
+
     def nbytes(self) -> int:
         n = self.embed.numel() + (0 if self.cfg.tie_embeddings else self.lm_head.numel())
         for L in self.layers:
@@ -357,13 +364,57 @@ class LlamaWeights:
                 if key not in seen:
                     seen.add(key)
                     total += t.untyped_storage().nbytes()
+        head_c = getattr(self, "lm_head_c", None)
         for t in (self.embed, getattr(self, "lm_head", None), getattr(self, "lm_head_p", None),
-                  self.final_norm):
+                  self.final_norm, head_c.wp if head_c is not None else None):
             add(t)
         for L in list(self.layers) + list(getattr(self, "decode_layers", [])):
             for t in L.values():
                 add(t)
         return total
+
+
+def gather_packed_rows(wp, rows: torch.Tensor):
+    """Rows ``rows`` (int64 [n], n % 16 == 0) of a decode GEMM weight, taken
+    in its packed layout: fragment-ordered bf16 [N/16, K/32, 64, 8] or an
+    ``ops.Fp8Weight`` ([N/16, K/64, 64, 16] bytes + a scale per row). In both
+    a 16-row tile holds row ``r`` in the lanes with ``lane & 15 == r``, so the
+    gather moves whole 8- / 16-element vectors between tiles and every byte
+    (and every fp8 row scale) is the source's: a gathered row's dot product is
+    bit for bit the full weight's."""
+    if isinstance(wp, ops.Fp8Weight):
+        return ops.Fp8Weight(gather_packed_rows(wp.wp, rows), wp.scale[rows].contiguous(),
+                             rows.numel(), wp.K)
+    T, KS, _, E = wp.shape
+    n = rows.numel()
+    assert n % 16 == 0 and int(rows.max()) < T * 16
+    g = wp.view(T, KS, 4, 16, E)[rows // 16, :, :, rows % 16]          # [n, KS, 4, E]
+    return g.view(n // 16, 16, KS, 4, E).permute(0, 2, 3, 1, 4).reshape(n // 16, KS, 64, E)
+
+
+class CompactHead:
+    """The lm_head rows of the tokens a grammar can select, in ascending token
+    id, in the decode GEMM's layout: constrained sampling streams these rows
+    instead of the whole vocabulary. ``ids`` int32 [n] (n a multiple of 16,
+    padded with a repeat of the last id; the sampler's mask keeps the padding
+    off), ``wp`` the packed rows (padded likewise to the 64-row tiles of the
+    Mpad 64 / 128 GEMMs), ``n`` the logits width."""
+
+    def __init__(self, lm_head_p, ids: torch.Tensor):
+        assert ids.dtype == torch.int32 and ids.dim() == 1 and ids.numel() % 16 == 0
+        self.ids = ids.to(lm_head_p.device).contiguous()
+        self.n = ids.numel()
+        rows = self.ids.long()
+        pad = -self.n % 64
+        if pad:
+            rows = torch.cat([rows, rows[-1:].expand(pad)])
+        self.wp = gather_packed_rows(lm_head_p, rows)
+
+    def rows(self) -> torch.Tensor:
+        """Row-major bf16 [n, K] (the CPU's plain ``linear``)."""
+        assert not isinstance(self.wp, ops.Fp8Weight)
+        T, KS, _, E = self.wp.shape
+        return self.wp.view(T, KS, 4, 16, E).permute(0, 3, 1, 2, 4).reshape(T * 16, KS * 4 * E)[:self.n]
 
 
 # prompt passes on the hand-written GEMMs (ops.proj: split-K tiled / weight-
@@ -512,13 +563,23 @@ class LlamaModel:
             t = self._ones_d = torch.ones(self.cfg.d_model, dtype=x.dtype, device=x.device)
         return t
 
+    def _head_logits(self, hf: torch.Tensor, head: "CompactHead | None") -> torch.Tensor:
+        """f32 logits of the final-normed rows ``hf`` [Mpad, d] on the decode
+        lm_head: the vocabulary (shard) [Mpad, V/tp], or with ``head`` its
+        columns only [Mpad, head.n]. One K pass either way (split 1), so a
+        token's logit does not depend on which of the two computed it."""
+        w = self.w
+        wp, n = (w.lm_head_p, w.v) if head is None else (head.wp, head.n)
+        return ops.skinny_gemm(hf, wp, 1, max_wgs=getattr(w, "max_wgs", ops.MAX_DECODE_WGS))[0][:, :n]
+
     def forward_decode(self, meta: StepMeta, k_cache: torch.Tensor, v_cache: torch.Tensor,
-                       attn_ws: ops.AttnWorkspace | None, split_keys: int = 128) -> torch.Tensor:
+                       attn_ws: ops.AttnWorkspace | None, split_keys: int = 128,
+                       head: "CompactHead | None" = None) -> torch.Tensor:
         """Decode / jump-forward step for <= 128 padded tokens. Every projection is
         the weight-streaming skinny MFMA GEMM emitting split-K f32 slabs that the
         following fused kernel reduces (rmsnorm+residual, RoPE+KV append, SwiGLU).
         ``meta.tokens`` has Mpad rows; ``meta.logit_idx`` has >= 16 rows.
-        Returns f32 logits [len(logit_idx), V/tp]."""
+        Returns f32 logits [len(logit_idx), V/tp] (``head``: [.., head.n])."""
         cfg, w, tp = self.cfg, self.w, self.w.tp
         H, Hkv, D = w.h, w.hkv, cfg.head_dim
         tp_splits = 1 if tp.world > 1 else None
@@ -548,19 +609,20 @@ class LlamaModel:
             tp.all_reduce_(down)
         hf = ops.slab_rmsnorm(down, residual, w.final_norm, cfg.norm_eps, row_idx=meta.logit_idx,
                               write_residual=False)
-        return ops.skinny_gemm(hf, w.lm_head_p, 1,
-                               max_wgs=getattr(w, "max_wgs", ops.MAX_DECODE_WGS))[0][:, :w.v]
+        return self._head_logits(hf, head)
 
     def forward_decode_fused(self, meta: StepMeta, k_cache: torch.Tensor, v_cache: torch.Tensor,
                              attn_ws: ops.AttnWorkspace | None, scratch: ops.FusedScratch,
-                             split_keys: int = 128) -> torch.Tensor:
+                             split_keys: int = 128,
+                             head: "CompactHead | None" = None) -> torch.Tensor:
         """Decode step with the fused-epilogue GEMMs (5 launches per layer):
         qkv (RMSNorm prologue, RoPE + KV append epilogue) -> attention ->
         o (residual + row sum-of-squares epilogue) -> gate|up (RMSNorm prologue,
         SwiGLU epilogue) -> down (residual + row sum-of-squares); Mpad 16 / 32 /
         64. Same numerics as ``forward_decode``. Tensor parallel:
         o and down emit bf16 partials and the residual all-reduce kernel adds
-        them (7 launches per layer); the logits are this rank's vocab slice."""
+        them (7 launches per layer); the logits are this rank's vocab slice.
+        ``head``: the logits of a compact sampling head's tokens only."""
         cfg, w, tp = self.cfg, self.w, self.w.tp
         H, Hkv, D, d = w.h, w.hkv, cfg.head_dim, cfg.d_model
         Mpad = meta.tokens.numel()
@@ -624,13 +686,13 @@ class LlamaModel:
             hf = ops.rmsnorm(residual, w.final_norm, cfg.norm_eps, row_idx=meta.logit_idx)
         else:
             hf = ops.rmsnorm(residual.index_select(0, meta.logit_idx), w.final_norm, cfg.norm_eps)
-        return ops.skinny_gemm(hf, w.lm_head_p, 1,
-                               max_wgs=getattr(w, "max_wgs", ops.MAX_DECODE_WGS))[0][:, :w.v]
+        return self._head_logits(hf, head)
 
-    def logits(self, hidden: torch.Tensor) -> torch.Tensor:
+    def logits(self, hidden: torch.Tensor, head: "CompactHead | None" = None) -> torch.Tensor:
         """Local vocab shard logits [B, V/tp]. On the GPU the prompt pass's few
         sampling rows go through the decode steps' weight-streaming lm_head
-        (pre-shuffled copy, rows padded to 16; f32 logits), not hipBLASLt."""
+        (pre-shuffled copy, rows padded to 16; f32 logits), not hipBLASLt.
+        ``head``: the logits of a compact sampling head's tokens [B, head.n]."""
         w = self.w
         B = hidden.shape[0]
         fp8 = isinstance(getattr(w, "lm_head_p", None), ops.Fp8Weight)   # the only lm_head copy
@@ -641,6 +703,5 @@ class LlamaModel:
             if Mpad != B:
                 x = torch.zeros(Mpad, hidden.shape[1], dtype=hidden.dtype, device=hidden.device)
                 x[:B] = hidden
-            return ops.skinny_gemm(x.contiguous(), w.lm_head_p, 1,
-                                   max_wgs=getattr(w, "max_wgs", ops.MAX_DECODE_WGS))[0][:B, :w.v]
-        return ops.linear(hidden, w.lm_head)
+            return self._head_logits(x.contiguous(), head)[:B]
+        return ops.linear(hidden, w.lm_head if head is None else head.rows())

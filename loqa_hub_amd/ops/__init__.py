@@ -261,12 +261,19 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_q: torch.Ten
 
 # ----------------------------------------------------------------- sampling
 def masked_argmax(logits: torch.Tensor, mask: torch.Tensor | None = None,
-                  mask_rows: torch.Tensor | None = None) -> torch.Tensor:
+                  mask_rows: torch.Tensor | None = None,
+                  token_ids: torch.Tensor | None = None) -> torch.Tensor:
     """argmax over tokens allowed by a packed uint32 bitmask (bit v%32 of word
     v//32). ``mask_rows`` optionally maps each logits row to a mask-table row.
-    Returns int32 [B] (-1 if nothing is allowed)."""
+    ``token_ids`` (int32 [V], ascending): the columns are a gathered subset of
+    the vocabulary (the compact sampling head; ``mask`` is in column order) and
+    the result is ``token_ids[column]``. Returns int32 [B] (-1 if nothing is
+    allowed)."""
+    if token_ids is not None:
+        assert token_ids.dtype == torch.int32 and token_ids.is_contiguous()
+        assert token_ids.numel() >= logits.shape[-1] and token_ids.device == logits.device
     if not _gpu(logits):
-        return ref.masked_argmax(logits, mask, mask_rows)
+        return ref.masked_argmax(logits, mask, mask_rows, token_ids)
     assert logits.dim() == 2 and logits.stride(-1) == 1
     B, V = logits.shape
     W = 0
@@ -284,7 +291,7 @@ def masked_argmax(logits: torch.Tensor, mask: torch.Tensor | None = None,
     ws = torch.empty(B, dtype=torch.int64, device=logits.device)
     check(kernels().loqa_masked_argmax(ptr(logits), int(is_bf16), logits.stride(0), B, V,
                                        ptr(mask), ptr(mask_rows), W, ptr(out), ptr(ws),
-                                       stream_ptr(logits)), "masked_argmax")
+                                       ptr(token_ids), stream_ptr(logits)), "masked_argmax")
     return out
 
 

@@ -141,7 +141,9 @@ def attention(q, k, v, cu_q, *, n_heads, n_kv, head_dim, causal, cu_k=None, ctx_
     return r
 
 
-def masked_argmax(logits, mask=None, mask_rows=None):
+def masked_argmax(logits, mask=None, mask_rows=None, token_ids=None):
+    """``token_ids``: the columns are a gathered vocabulary subset; the result
+    is the token id of the winning column (lowest column on a tie)."""
     x = logits.float()
     B, V = x.shape
     if mask is not None:
@@ -152,6 +154,8 @@ def masked_argmax(logits, mask=None, mask_rows=None):
     else:
         none = torch.zeros(B, dtype=torch.bool, device=x.device)
     r = x.argmax(dim=-1).to(torch.int32)
+    if token_ids is not None:
+        r = token_ids.to(torch.int32)[r.long()]
     r[none] = -1
     return r
 

@@ -8,7 +8,7 @@ import re
 import sys
 
 LLM = re.compile(r"skinny_fused_kernel<\d, \d+, \d, \d, \d, \d(, 0)?>|attn_decode_kernel<128|"
-                 r"skinny_gemm_kernel<2, 1, 4>|masked_argmax_kernel<true>|step_fetch|step_publish")
+                 r"skinny_gemm_kernel<2, 1, 4>|masked_argmax_kernel<true|step_fetch|step_publish")
 
 
 def classify(name: str) -> str:
@@ -17,10 +17,10 @@ def classify(name: str) -> str:
         u = re.search(r"skinny_fused_kernel<\d, \d+, (\d),", name)
         return "llm" if u and u.group(1) == "4" else "stt"
     if "attn_decode_kernel<128" in name or "skinny_gemm_kernel<2, 1, 4>" in name or \
-            "step_fetch" in name or "step_publish" in name or "masked_argmax_kernel<true>" in name:
+            "step_fetch" in name or "step_publish" in name or "masked_argmax_kernel<true" in name:
         return "llm"
     if "attn_decode_kernel<64" in name or "skinny_gemm_kernel<2, 1, 2>" in name or \
-            "masked_argmax_kernel<false>" in name:
+            "masked_argmax_kernel<false" in name:
         return "stt"
     return "other"
 
