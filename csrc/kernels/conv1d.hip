@@ -282,6 +282,22 @@ __global__ __launch_bounds__(256) void conv1d_lds_kernel(ConvArgs p) {
   if (t0 < p.Tq) conv_epilogue(p, acc, b, t0, co0, lane);
 }
 
+static size_t conv_lds_bytes(int K, int dil, int cc) {
+  return (size_t)(128 + (K - 1) * dil + 32 * K) * (cc + 8) * sizeof(bf16_t);
+}
+
+// Which kernel serves a conv: 0 the register form, 64 / 32 the LDS form with
+// that many channels per chunk. LDS form: stride 1, staged rows R <= 256 and
+// K <= 16; 64-channel chunks when the staged rows + weight slice fit in 64 KiB
+// (two workgroups per CU), else 32-channel chunks.
+extern "C" int loqa_conv1d_form(int Cin, int K, int dil, int stride) {
+  if (stride == 1 && Cin % 32 == 0 && 128 + (K - 1) * dil <= 256 && K <= 16) {
+    if (Cin % 64 == 0 && conv_lds_bytes(K, dil, 64) <= 64 * 1024) return 64;
+    if (conv_lds_bytes(K, dil, 32) <= 64 * 1024) return 32;
+  }
+  return 0;
+}
+
 extern "C" int loqa_conv1d(const void* x, long long xb, int ldx, const void* w, const void* bias,
                            void* y, long long yb, int ldy, const void* res, long long rb, int ldr,
                            const void* acc, long long ab, int lda, const int* lens, int B, int Tin,
@@ -298,20 +314,12 @@ extern "C" int loqa_conv1d(const void* x, long long xb, int ldx, const void* w, 
              K, dil, pad, stride, ostride, ophase, Tout, pre_act, pre_slope, post_act, alpha,
              out_pcm16, cout_real};
   dim3 grid((Tq + 127) / 128, Cout / 32, B);
-  if (stride == 1 && Cin % 32 == 0 && 128 + (K - 1) * dil <= 256 && K <= 16) {
-    // LDS form: 64-channel chunks when the staged rows + weight slice fit in
-    // 64 KiB (two workgroups per CU), else 32-channel chunks
-    const int R = 128 + (K - 1) * dil;
-    auto lds_of = [&](int cc) { return (size_t)(R + 32 * K) * (cc + 8) * sizeof(bf16_t); };
-    if (Cin % 64 == 0 && lds_of(64) <= 64 * 1024) {
-      hipLaunchKernelGGL(conv1d_lds_kernel<64>, grid, dim3(256), lds_of(64), s, p);
-      return (int)hipGetLastError();
-    }
-    if (lds_of(32) <= 64 * 1024) {
-      hipLaunchKernelGGL(conv1d_lds_kernel<32>, grid, dim3(256), lds_of(32), s, p);
-      return (int)hipGetLastError();
-    }
-  }
-  hipLaunchKernelGGL(conv1d_mfma_kernel, grid, dim3(256), 0, s, p);
+  const int form = loqa_conv1d_form(Cin, K, dil, stride);
+  if (form == 64)
+    hipLaunchKernelGGL(conv1d_lds_kernel<64>, grid, dim3(256), conv_lds_bytes(K, dil, 64), s, p);
+  else if (form == 32)
+    hipLaunchKernelGGL(conv1d_lds_kernel<32>, grid, dim3(256), conv_lds_bytes(K, dil, 32), s, p);
+  else
+    hipLaunchKernelGGL(conv1d_mfma_kernel, grid, dim3(256), 0, s, p);
   return (int)hipGetLastError();
 }

@@ -1093,6 +1093,10 @@ def expand_sample(stats: torch.Tensor, cum: torch.Tensor, flen: torch.Tensor, F:
         noise = torch.randn(B, F, C2 // 2, generator=g)
         return ref.expand_sample(stats, cum, flen, F, noise_scale, noise).to(torch.bfloat16)
     assert cum.dtype == torch.int32 and flen.dtype == torch.int32
+    # the kernel addresses row (b, i) at (b * T + i) * ld: no batch stride of its own
+    assert stats.dtype == torch.bfloat16 and stats.stride(2) == 1
+    assert B == 1 or stats.stride(0) == T * stats.stride(1), "stats: batch stride must be T * row stride"
+    assert cum.is_contiguous() and cum.shape == (B, T) and flen.is_contiguous()
     z = torch.empty(B, F, C2 // 2, dtype=torch.bfloat16, device=stats.device)
     check(kernels().loqa_expand_sample(ptr(stats), stats.stride(1), ptr(cum), B, T, ptr(flen),
                                        ptr(z), F, C2 // 2, float(noise_scale), seed & 0xFFFFFFFF,

@@ -133,6 +133,7 @@ _KERNEL_SIGS = {
                     c_ll, c_int, c_void_p, c_ll, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int,
                     c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int,
                     c_float, c_int, c_int, c_void_p],
+    "loqa_conv1d_form": [c_int, c_int, c_int, c_int],
     "loqa_relpos_attention": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                               c_int, c_int, c_int, c_int, c_int, c_float, c_void_p],
     "loqa_expand_sample": [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int,

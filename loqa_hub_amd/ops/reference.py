@@ -425,7 +425,8 @@ def conv1d(x, w, bias=None, *, dil=1, pad=0, stride=1, pre_slope=None, act=None,
         full[:, idx] += acc[:, idx].float()
     if lens is not None:
         t = torch.arange(T_out, device=x.device)
-        full = full * (t[None, :] < lens[:, None].to(x.device)).float()[..., None]
+        # a select, not a multiply: rows past lens are 0 whatever res / acc hold there
+        full = full.masked_fill((t[None, :] >= lens[:, None].to(x.device))[..., None], 0.0)
     return full
 
 
