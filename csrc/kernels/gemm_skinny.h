@@ -28,15 +28,14 @@
 // launch priority of the calling host thread (attn_decode.hip)
 extern thread_local int g_loqa_launch_prio;
 
-typedef float float4v_ __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ float4v_ mfma16(const bf16x8& a, const bf16x8& b, const float4v_& c) {
+__device__ __forceinline__ float4v mfma16(const bf16x8& a, const bf16x8& b, const float4v& c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 
-// streamed-once weights: non-temporal load
-__device__ __forceinline__ bf16x8 ldw(const bf16_t* p) {
+// streamed-once weights: non-temporal 16-byte load (8 bf16, or 16 raw fp8 bytes)
+__device__ __forceinline__ bf16x8 ldw(const void* p) {
   u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
   return *reinterpret_cast<bf16x8*>(&v);
 }
@@ -49,11 +48,6 @@ __device__ __forceinline__ bf16x8 ldw(const bf16_t* p) {
 // every e4m3 value is a bf16 value - when its group is consumed.
 typedef unsigned char fp8_t;
 template <typename W> constexpr int kFp8 = sizeof(W) == 1;
-
-__device__ __forceinline__ bf16x8 ldw(const fp8_t* p) {
-  u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
-  return *reinterpret_cast<bf16x8*>(&v);
-}
 
 // 8 e4m3 bytes -> the 8 bf16 of one MFMA A fragment: gfx950's packed
 // fp8 -> bf16 convert with scale 1.0, two values per instruction (checked on
@@ -100,21 +94,27 @@ __device__ __forceinline__ void lds_barrier() {
   asm volatile("" ::: "memory");
 }
 
+// One prefetch group of weights: U k-steps of RT row tiles.
 // NW: 16-byte weight loads per row tile and group (fp8: one per two k-steps)
-template <int RT, int MT, int U, int FP8 = 0>
-struct Frag {
+template <int RT, int U, int FP8 = 0>
+struct WFrag {
   static constexpr int NW = FP8 ? (U + 1) / 2 : U;
   bf16x8 a[NW][RT];
+};
+
+// ... and the group's activation fragments (the register form; XL reads them from LDS)
+template <int RT, int MT, int U, int FP8 = 0>
+struct Frag : WFrag<RT, U, FP8> {
   bf16x8 b[U][MT];
 };
 
 // wp: this lane's 16 bytes of the tile's first k-step; in elements of W a
 // k-step is 512 apart in both formats (fp8: ks even)
-template <int RT, int MT, int U, int FP8, typename W>
-__device__ __forceinline__ void load_frag_w(Frag<RT, MT, U, FP8>& f, const W* wp, size_t tile_stride, int ks) {
+template <int RT, int U, int FP8, typename W>
+__device__ __forceinline__ void load_w(WFrag<RT, U, FP8>& f, const W* wp, size_t tile_stride, int ks) {
   static_assert(FP8 == kFp8<W>, "fragment / weight format mismatch");
 #pragma unroll
-  for (int u = 0; u < Frag<RT, MT, U, FP8>::NW; ++u)
+  for (int u = 0; u < WFrag<RT, U, FP8>::NW; ++u)
 #pragma unroll
     for (int i = 0; i < RT; ++i)
       f.a[u][i] = ldw(wp + (size_t)i * tile_stride + (size_t)(ks + u * (FP8 ? 2 : 1)) * 512);
@@ -131,45 +131,55 @@ __device__ __forceinline__ void load_frag_x(Frag<RT, MT, U, FP8>& f, const bf16_
 template <int RT, int MT, int U, int FP8, typename W>
 __device__ __forceinline__ void load_frag(Frag<RT, MT, U, FP8>& f, const W* wp, size_t tile_stride,
                                           const bf16_t* xp, long long ldx_, int ks) {
-  load_frag_w(f, wp, tile_stride, ks);
+  load_w<RT, U, FP8>(f, wp, tile_stride, ks);
   load_frag_x(f, xp, ldx_, ks);
 }
 
+// k-step u of a group against its MT activation fragments. fp8: this
+// k-step's A fragments are dequantised once, here (k-steps stay in ascending
+// order). bf16 reads the prefetch registers in place: going through the same
+// local copy is not free - it took skinny_fused_kernel<1, 2, 4, 4, act> from
+// occupancy 4 to 3 (docs/PERF.md, "Decode GEMM header")
 template <int RT, int MT, int U, int FP8>
-__device__ __forceinline__ void mma_frag(const Frag<RT, MT, U, FP8>& f, float4v_ (&acc)[RT][MT]) {
+__device__ __forceinline__ void mma_step(const WFrag<RT, U, FP8>& f, int u, const bf16x8 (&b)[MT],
+                                         float4v (&acc)[RT][MT]) {
+  bf16x8 deq[FP8 ? RT : 1];
+  if constexpr (FP8) {
 #pragma unroll
-  for (int u = 0; u < U; ++u) {
-    if constexpr (FP8) {
-      // dequantise this k-step's A fragments (k-steps stay in ascending order)
-      bf16x8 a[RT];
-#pragma unroll
-      for (int i = 0; i < RT; ++i) a[i] = wfrag<1>(f.a[u / 2][i], u);
-#pragma unroll
-      for (int j = 0; j < MT; ++j)
-#pragma unroll
-        for (int i = 0; i < RT; ++i) acc[i][j] = mfma16(a[i], f.b[u][j], acc[i][j]);
-    } else {
-#pragma unroll
-      for (int j = 0; j < MT; ++j)
-#pragma unroll
-        for (int i = 0; i < RT; ++i) acc[i][j] = mfma16(f.a[u][i], f.b[u][j], acc[i][j]);
-    }
+    for (int i = 0; i < RT; ++i) deq[i] = wfrag<1>(f.a[u / 2][i], u);
   }
+  auto a = [&](int i) -> const bf16x8& {
+    if constexpr (FP8) return deq[i];
+    else return f.a[u][i];
+  };
+#pragma unroll
+  for (int j = 0; j < MT; ++j)
+#pragma unroll
+    for (int i = 0; i < RT; ++i) acc[i][j] = mfma16(a(i), b[j], acc[i][j]);
 }
 
-// Ping-pong stream over ng groups of U k-steps; f0 already holds group
-// ``rot`` (groups are visited in the rotated order rot, rot+1, ... mod ng).
+template <int RT, int MT, int U, int FP8>
+__device__ __forceinline__ void mma_frag(const Frag<RT, MT, U, FP8>& f, float4v (&acc)[RT][MT]) {
+#pragma unroll
+  for (int u = 0; u < U; ++u) mma_step<RT, MT, U, FP8>(f, u, f.b[u], acc);
+}
+
+// Ping-pong stream over ng groups of U k-steps from k-step ks0; f0 already
+// holds group 0.
 // The steady-state loop issues the next group UNCONDITIONALLY before consuming
 // the current one: a conditional refill inside the loop body makes the
 // consumer block a join point of the refill / no-refill paths, and hipcc's
 // waitcnt pass then takes the stricter count of the two (vmcnt(0)) - every
 // iteration drained the prefetch and only ONE group was ever in flight.
+// (Groups are visited in ascending order. A k-start rotation per workgroup
+// measured 5-10 % SLOWER on every shape: the in-step x reuse across
+// neighbouring workgroups in L2 matters more.)
 template <int RT, int MT, int U, int FP8, typename W>
 __device__ __forceinline__ void stream_k(Frag<RT, MT, U, FP8>& f0, Frag<RT, MT, U, FP8>& f1,
-                                         float4v_ (&acc)[RT][MT], const W* wp,
+                                         float4v (&acc)[RT][MT], const W* wp,
                                          size_t tile_stride, const bf16_t* xp, long long ldx_,
-                                         int ks0, int ng, int rot) {
-  auto ks = [&](int g) { int q = g + rot; q -= q >= ng ? ng : 0; return ks0 + q * U; };
+                                         int ks0, int ng) {
+  auto ks = [&](int g) { return ks0 + g * U; };
   // sched_barrier(0) pins each phase: without it the machine scheduler sinks
   // the refill loads between the MFMAs to save registers, collapsing the
   // prefetch distance to 3-5 loads
@@ -197,7 +207,7 @@ __device__ __forceinline__ void stream_k(Frag<RT, MT, U, FP8>& f0, Frag<RT, MT, 
 // wscale (fp8 only): f32 [N] per-row dequantisation scale, applied as wave 0
 // writes its slab
 template <int RT, int MT, int U, typename W>
-__device__ __forceinline__ void skinny_gemm_body(float4v_ (&red)[3][RT * MT][64],
+__device__ __forceinline__ void skinny_gemm_body(float4v (&red)[3][RT * MT][64],
                                                  const bf16_t* __restrict__ x, long long ldx_,
                                                  const W* __restrict__ Wp, const float* __restrict__ wscale,
                                                  float* __restrict__ part, int N, int K, int S, int Mpad) {
@@ -215,16 +225,16 @@ __device__ __forceinline__ void skinny_gemm_body(float4v_ (&red)[3][RT * MT][64]
   for (int tg = blockIdx.x; tg < ngroups; tg += gridDim.x) {
     const int tile0 = tg * RT;                  // first 16-row tile
     const W* wp = Wp + (size_t)tile0 * tile_stride + (size_t)lane * (FP8 ? 16 : 8);
-    float4v_ acc[RT][MT];
+    float4v acc[RT][MT];
 #pragma unroll
     for (int i = 0; i < RT; ++i)
 #pragma unroll
-      for (int j = 0; j < MT; ++j) acc[i][j] = (float4v_){0.f, 0.f, 0.f, 0.f};
+      for (int j = 0; j < MT; ++j) acc[i][j] = (float4v){0.f, 0.f, 0.f, 0.f};
 
     // ping-pong register prefetch over groups of U k-steps
     Frag<RT, MT, U, FP8> f0, f1;
     load_frag(f0, wp, tile_stride, xp, ldx_, ks0);
-    stream_k(f0, f1, acc, wp, tile_stride, xp, ldx_, ks0, kw / U, 0);
+    stream_k(f0, f1, acc, wp, tile_stride, xp, ldx_, ks0, kw / U);
 
     if (wave > 0) {
 #pragma unroll
@@ -238,13 +248,13 @@ __device__ __forceinline__ void skinny_gemm_body(float4v_ (&red)[3][RT * MT][64]
       for (int i = 0; i < RT; ++i)
 #pragma unroll
         for (int j = 0; j < MT; ++j) {
-          float4v_ v = acc[i][j] + red[0][i * MT + j][lane] + red[1][i * MT + j][lane] +
-                       red[2][i * MT + j][lane];
+          float4v v = acc[i][j] + red[0][i * MT + j][lane] + red[1][i * MT + j][lane] +
+                      red[2][i * MT + j][lane];
           // C layout (16x16): col = lane&15 (token m), rows n = 4*(lane>>4) + reg
           const int m = j * 16 + (lane & 15);
           const int n = (tile0 + i) * 16 + 4 * (lane >> 4);
-          if constexpr (FP8) v *= *reinterpret_cast<const float4v_*>(wscale + n);
-          *reinterpret_cast<float4v_*>(part + ((size_t)s * Mpad + m) * N + n) = v;
+          if constexpr (FP8) v *= *reinterpret_cast<const float4v*>(wscale + n);
+          *reinterpret_cast<float4v*>(part + ((size_t)s * Mpad + m) * N + n) = v;
         }
     }
     __syncthreads();                            // red is reused by the next group
@@ -256,62 +266,67 @@ __global__ __launch_bounds__(256) void skinny_gemm_kernel(const bf16_t* __restri
                                                           const bf16_t* __restrict__ Wp,
                                                           float* __restrict__ part, int N, int K,
                                                           int S, int Mpad) {
-  __shared__ float4v_ red[3][RT * MT][64];
+  __shared__ float4v red[3][RT * MT][64];
   skinny_gemm_body<RT, MT, U>(red, x, ldx_, Wp, nullptr, part, N, K, S, Mpad);
 }
 
+// the fp8 weight stream: its own kernel name, so the bf16 instances keep theirs
 template <int RT, int MT, int U>
 __global__ __launch_bounds__(256) void skinny_gemm_fp8_kernel(const bf16_t* __restrict__ x, long long ldx_,
                                                               const fp8_t* __restrict__ Wp,
                                                               const float* __restrict__ wscale,
                                                               float* __restrict__ part, int N, int K,
                                                               int S, int Mpad) {
-  __shared__ float4v_ red[3][RT * MT][64];
+  __shared__ float4v red[3][RT * MT][64];
   skinny_gemm_body<RT, MT, U>(red, x, ldx_, Wp, wscale, part, N, K, S, Mpad);
 }
 
-template <int RT, int MT>
-static int launch_skinny(const void* x, long long ldx_, const void* Wp, float* part, int N, int K,
-                         int S, int Mpad, int max_wgs, hipStream_t st) {
-  int gx = N / (16 * RT);
-  if (max_wgs > 0 && gx * S > max_wgs) gx = max_wgs / S > 0 ? max_wgs / S : 1;
-  dim3 grid(gx, S);
-  const int kw = K / 32 / (S * 4);
-  if constexpr (MT <= 2) {
-    if (kw % 4 == 0) {
-      hipLaunchKernelGGL((skinny_gemm_kernel<RT, MT, 4>), grid, dim3(256), 0, st, (const bf16_t*)x,
-                         ldx_, (const bf16_t*)Wp, part, N, K, S, Mpad);
-      return (int)hipGetLastError();
-    }
-  }
-  if (kw % 2 == 0)
-    hipLaunchKernelGGL((skinny_gemm_kernel<RT, MT, 2>), grid, dim3(256), 0, st, (const bf16_t*)x,
-                       ldx_, (const bf16_t*)Wp, part, N, K, S, Mpad);
+struct SkinnyArgs {
+  const void* x; long long ldx; const void* Wp; const float* wscale; float* part;
+  int N, K, S, Mpad, max_wgs;
+};
+
+template <int RT, int MT, int U, typename W>
+static void launch_skinny_kernel(dim3 grid, const SkinnyArgs& a, hipStream_t st) {
+  if constexpr (kFp8<W>)
+    hipLaunchKernelGGL((skinny_gemm_fp8_kernel<RT, MT, U>), grid, dim3(256), 0, st, (const bf16_t*)a.x,
+                       a.ldx, (const fp8_t*)a.Wp, a.wscale, a.part, a.N, a.K, a.S, a.Mpad);
   else
-    hipLaunchKernelGGL((skinny_gemm_kernel<RT, MT, 1>), grid, dim3(256), 0, st, (const bf16_t*)x,
-                       ldx_, (const bf16_t*)Wp, part, N, K, S, Mpad);
+    hipLaunchKernelGGL((skinny_gemm_kernel<RT, MT, U>), grid, dim3(256), 0, st, (const bf16_t*)a.x,
+                       a.ldx, (const bf16_t*)a.Wp, a.part, a.N, a.K, a.S, a.Mpad);
+}
+
+// Prefetch groups of 4 k-steps (MT <= 2), of 2 or 1 when the wave's k range
+// does not divide. fp8 weights: the same grid and prefetch groups; a wave's k
+// range must be even
+template <int RT, int MT, typename W>
+static int launch_skinny(const SkinnyArgs& a, hipStream_t st) {
+  int gx = a.N / (16 * RT);
+  if (a.max_wgs > 0 && gx * a.S > a.max_wgs) gx = a.max_wgs / a.S > 0 ? a.max_wgs / a.S : 1;
+  dim3 grid(gx, a.S);
+  const int kw = a.K / 32 / (a.S * 4);
+  if (MT <= 2 && kw % 4 == 0)
+    launch_skinny_kernel<RT, MT, (MT <= 2 ? 4 : 2), W>(grid, a, st);
+  else if (kw % 2 == 0)
+    launch_skinny_kernel<RT, MT, 2, W>(grid, a, st);
+  else if constexpr (!kFp8<W>)
+    launch_skinny_kernel<RT, MT, 1, W>(grid, a, st);
+  else
+    return (int)hipErrorInvalidValue;
   return (int)hipGetLastError();
 }
 
-// fp8 weights: the same grid and prefetch groups; a wave's k range must be even
-template <int RT, int MT>
-static int launch_skinny_fp8(const void* x, long long ldx_, const void* Wp, const float* wscale,
-                             float* part, int N, int K, int S, int Mpad, int max_wgs, hipStream_t st) {
-  int gx = N / (16 * RT);
-  if (max_wgs > 0 && gx * S > max_wgs) gx = max_wgs / S > 0 ? max_wgs / S : 1;
-  dim3 grid(gx, S);
-  const int kw = K / 32 / (S * 4);
-  if (kw % 2) return (int)hipErrorInvalidValue;
-  if constexpr (MT <= 2) {
-    if (kw % 4 == 0) {
-      hipLaunchKernelGGL((skinny_gemm_fp8_kernel<RT, MT, 4>), grid, dim3(256), 0, st, (const bf16_t*)x,
-                         ldx_, (const fp8_t*)Wp, wscale, part, N, K, S, Mpad);
-      return (int)hipGetLastError();
-    }
+// Mpad -> (RT, MT) of the plain skinny GEMM, both weight formats
+template <typename W>
+static int dispatch_skinny(const SkinnyArgs& a, hipStream_t st) {
+  if (a.N % (a.Mpad >= 64 ? 64 : 32)) return (int)hipErrorInvalidValue;
+  switch (a.Mpad) {
+    case 16: return launch_skinny<2, 1, W>(a, st);
+    case 32: return launch_skinny<2, 2, W>(a, st);
+    case 64: return launch_skinny<4, 4, W>(a, st);
+    case 128: return launch_skinny<4, 8, W>(a, st);
+    default: return (int)hipErrorInvalidValue;
   }
-  hipLaunchKernelGGL((skinny_gemm_fp8_kernel<RT, MT, 2>), grid, dim3(256), 0, st, (const bf16_t*)x,
-                     ldx_, (const fp8_t*)Wp, wscale, part, N, K, S, Mpad);
-  return (int)hipGetLastError();
 }
 
 // ============================================================================
@@ -334,22 +349,6 @@ static int launch_skinny_fp8(const void* x, long long ldx_, const void* Wp, cons
 // 32-bank rules: SQ_LDS_BANK_CONFLICT measured ~1 extra cycle per cycle.)
 constexpr int XROW = 32;   // LDS row: 32 k values (64 B), pieces swizzled
 __device__ __forceinline__ int xs_piece(int row, int q) { return (q ^ ((row >> 1) & 3)) * 8; }
-
-template <int RT, int U, int FP8 = 0>
-struct WFrag {
-  static constexpr int NW = FP8 ? (U + 1) / 2 : U;   // as Frag
-  bf16x8 a[NW][RT];
-};
-
-template <int RT, int U, int FP8, typename W>
-__device__ __forceinline__ void load_w(WFrag<RT, U, FP8>& f, const W* wp, size_t tile_stride, int ks) {
-  static_assert(FP8 == kFp8<W>, "fragment / weight format mismatch");
-#pragma unroll
-  for (int u = 0; u < WFrag<RT, U, FP8>::NW; ++u)
-#pragma unroll
-    for (int i = 0; i < RT; ++i)
-      f.a[u][i] = ldw(wp + (size_t)i * tile_stride + (size_t)(ks + u * (FP8 ? 2 : 1)) * 512);
-}
 
 // one chunk of x: U k-steps x MP rows = MP * U * 4 pieces of 16 B
 template <int MP, int U>
@@ -390,7 +389,7 @@ __device__ __forceinline__ void store_xc(const XRegs<MP, U>& r, bf16_t* xs) {
 }
 
 template <int RT, int MT, int U, int FP8>
-__device__ __forceinline__ void mma_xl(const WFrag<RT, U, FP8>& f, float4v_ (&acc)[RT][MT], const bf16_t* xs,
+__device__ __forceinline__ void mma_xl(const WFrag<RT, U, FP8>& f, float4v (&acc)[RT][MT], const bf16_t* xs,
                                        int lane) {
 #pragma unroll
   for (int u = 0; u < U; ++u) {
@@ -399,20 +398,7 @@ __device__ __forceinline__ void mma_xl(const WFrag<RT, U, FP8>& f, float4v_ (&ac
     for (int j = 0; j < MT; ++j)
       b[j] = *reinterpret_cast<const bf16x8*>(xs + (size_t)(u * MT * 16 + j * 16 + (lane & 15)) * XROW +
                                               xs_piece(lane & 15, lane >> 4));
-    if constexpr (FP8) {
-      bf16x8 a[RT];
-#pragma unroll
-      for (int i = 0; i < RT; ++i) a[i] = wfrag<1>(f.a[u / 2][i], u);
-#pragma unroll
-      for (int j = 0; j < MT; ++j)
-#pragma unroll
-        for (int i = 0; i < RT; ++i) acc[i][j] = mfma16(a[i], b[j], acc[i][j]);
-    } else {
-#pragma unroll
-      for (int j = 0; j < MT; ++j)
-#pragma unroll
-        for (int i = 0; i < RT; ++i) acc[i][j] = mfma16(f.a[u][i], b[j], acc[i][j]);
-    }
+    mma_step(f, u, b, acc);
   }
 }
 
@@ -423,7 +409,7 @@ __device__ __forceinline__ void mma_xl(const WFrag<RT, U, FP8>& f, float4v_ (&ac
 // current chunk from LDS, then (barrier) overwrite LDS with the next chunk.
 template <int RT, int MT, int U, int FP8, typename W>
 __device__ __forceinline__ void stream_k_xl(WFrag<RT, U, FP8>& f0, WFrag<RT, U, FP8>& f1, XRegs<MT * 16, U>& xr,
-                                            float4v_ (&acc)[RT][MT], const W* wp,
+                                            float4v (&acc)[RT][MT], const W* wp,
                                             size_t tile_stride, const bf16_t* x, long long ldx_,
                                             bf16_t* xs, int ks0, int ng, int lane) {
   auto ks = [&](int g) { return ks0 + (g < ng ? g : ng - 1) * U; };
@@ -483,8 +469,10 @@ __device__ __forceinline__ void stream_k_xl(WFrag<RT, U, FP8>& f0, WFrag<RT, U, 
 // per-tile partial sums of squares in a fixed order (deterministic, no atomics).
 // Weight rows are permuted at load time so one 32-row tile holds (gate, up)
 // feature pairs, or the (c, c + D/2) RoPE pairs of one head.
-typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
-enum { EPI_SILU = 1, EPI_RESID = 2, EPI_ROPE = 3, EPI_ACT = 4 };
+//
+// The epilogue modes (FusedParams::mode; Python passes the numbers). FEPI_, not
+// EPI_: gemm_mfma.h numbers the prompt-pass epilogues differently.
+enum { FEPI_SILU = 1, FEPI_RESID = 2, FEPI_ROPE = 3, FEPI_ACT = 4 };
 enum { NORM_NONE = 0, NORM_RMS = 1, NORM_LN = 2 };
 
 // Host-side parameter block (mirrored by a ctypes.Structure in ops/_lib.py).
@@ -510,10 +498,10 @@ struct FusedArgs {
   int* counters;
   const float* rowsq_in; const float* rowsum_in; int rowstat_tiles; float eps;  // norm row stats
   const float* colsum; const float* bias;   // LayerNorm mean correction, output bias (per row of W)
-  bf16_t* out; long long ldo; int act;                                        // EPI_SILU / EPI_ACT
-  bf16_t* residual; float* rowsq_out; float* rowsum_out;                      // EPI_RESID
+  bf16_t* out; long long ldo; int act;                                        // FEPI_SILU / FEPI_ACT
+  bf16_t* residual; float* rowsq_out; float* rowsum_out;                      // FEPI_RESID
   const int* positions; const float2* cs; bf16_t* q_out; bf16_t* kc; bf16_t* vc;
-  const int* slots; int H, Hkv, D, blk;                                       // EPI_ROPE
+  const int* slots; int H, Hkv, D, blk;                                       // FEPI_ROPE
   int prio;                                     // s_setprio 3 for the launch (attn_decode.hip)
   const float* wscale;                          // fp8 weight stream: per-row scale (else unused)
 };
@@ -532,8 +520,22 @@ struct FusedSmem {
   static constexpr int NSM = NRED * 4 > 1024 ? NRED * 4 : 1024;   // floats: reduce / prologue / ticket
 };
 
+// sred (the first 1024 floats of the workgroup's LDS) in the norm prologue:
+// [0, 512) per-thread partial sums of squares, [512, 768) partial row sums,
+// then the finished row scales and the row means, up to Mpad 128 rows each
+constexpr int SRED_SUM = 512, SRED_SCALE = 768, SRED_MEAN = 896;
+
 // One (16 * RT * WR)-row output tile of the fused GEMM (a workgroup's whole
-// GEMM work; `return` = this workgroup's GEMM part is done)
+// GEMM work; `return` = this workgroup's GEMM part is done).
+// One long function on purpose: its sections (operand requests, norm prologue,
+// k loop, cross-wave and split-K reduce, the scale / norm / bias step and the
+// four epilogues) were each tried as a __forceinline__ function over the same
+// arrays, and every one of them moved the registers of some instances - one
+// to a lower occupancy (docs/PERF.md, "Decode GEMM header").
+// The epilogues see one wave's accumulators in the 16x16 MFMA C layout,
+// acc[i][j][r] = C[16 * i + nq + r][16 * j + (lane & 15)], nq = 4 * (lane >> 4):
+// column = token, rows = 4 consecutive features per lane - the layout the
+// prompt-pass GEMMs (gemm_mfma.h) also produce.
 template <int RT, int MT, int U, int WR, int MODE, int NORM, int XL, int FP8 = 0>
 __device__ __forceinline__ void skinny_fused_tile(const FusedArgs& a, float* smem, bf16_t* xs, const int bx,
                                                   const int by) {
@@ -541,8 +543,8 @@ __device__ __forceinline__ void skinny_fused_tile(const FusedArgs& a, float* sme
   static_assert(!XL || WR == 4, "XL needs the 4 waves along rows");
   // XL + RoPE at MT 8: the RoPE cos/sin operands (RT * MT * 8 VGPRs) are
   // loaded after the k loop instead of being held through it
-  constexpr bool EARLY_EPI = !(XL && MODE == EPI_ROPE && MT > 4);
-  float4v_* red = reinterpret_cast<float4v_*>(smem);
+  constexpr bool EARLY_EPI = !(XL && MODE == FEPI_ROPE && MT > 4);
+  float4v* red = reinterpret_cast<float4v*>(smem);
   float* sred = smem;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wr = wave % WR, wk = wave / WR;
@@ -564,14 +566,11 @@ __device__ __forceinline__ void skinny_fused_tile(const FusedArgs& a, float* sme
   WFrag<RT, XL ? U : 1, FP8> w0, w1;
   XRegs<XL ? MT * 16 : 64, XL ? U : 1> xr;
   const int ng = kw / U;
-  // (a k-start rotation per workgroup measured 5-10 % SLOWER on every shape:
-  // the in-step x reuse across neighbouring workgroups in L2 matters more)
-  const int rot = 0;
   if constexpr (XL) {
     load_xc<MT * 16, U>(xr, a.x, a.ldx, ks0);      // x first: storing it waits for x only
     load_w(w0, wp, tile_stride, ks0);
   } else {
-    load_frag(f0, wp, tile_stride, xp, a.ldx, ks0 + rot * U);
+    load_frag(f0, wp, tile_stride, xp, a.ldx, ks0);
   }
 
   // Epilogue operands (residual tile, bias, LayerNorm column sums, RoPE
@@ -640,14 +639,14 @@ __device__ __forceinline__ void skinny_fused_tile(const FusedArgs& a, float* sme
       for (int i = 0; i < RT; ++i)
         cvec[i] = *reinterpret_cast<const float4*>(a.colsum + tile * (16 * RT) + i * 16 + nq);
     }
-    if constexpr (MODE == EPI_RESID) {
+    if constexpr (MODE == FEPI_RESID) {
 #pragma unroll
       for (int j = 0; j < MT; ++j)
 #pragma unroll
         for (int i = 0; i < RT; ++i)
           rres[i][j] = *reinterpret_cast<const uint2*>(
               a.residual + (size_t)(j * 16 + (lane & 15)) * a.N + tile * (16 * RT) + i * 16 + nq);
-    } else if constexpr (MODE == EPI_ROPE && EARLY_EPI) {
+    } else if constexpr (MODE == FEPI_ROPE && EARLY_EPI) {
       load_rope_ops();
     }
   }
@@ -679,38 +678,38 @@ __device__ __forceinline__ void skinny_fused_tile(const FusedArgs& a, float* sme
       }
     }
     sred[g * Mp + m] = aq;
-    if constexpr (NORM == NORM_LN) sred[512 + g * Mp + m] = as;
+    if constexpr (NORM == NORM_LN) sred[SRED_SUM + g * Mp + m] = as;
     lds_barrier();
     if (threadIdx.x < Mp) {
       float tq = 0.f, ts = 0.f;
       for (int q = 0; q < G; ++q) {
         tq += sred[q * Mp + threadIdx.x];
-        if constexpr (NORM == NORM_LN) ts += sred[512 + q * Mp + threadIdx.x];
+        if constexpr (NORM == NORM_LN) ts += sred[SRED_SUM + q * Mp + threadIdx.x];
       }
       const float mean = ts / (float)a.K;
       const float var = fmaxf(tq / (float)a.K - mean * mean, 0.f);
-      sred[768 + threadIdx.x] = rsqrtf(var + a.eps);   // [768, 896): up to Mpad 128 rows
-      sred[896 + threadIdx.x] = mean;
+      sred[SRED_SCALE + threadIdx.x] = rsqrtf(var + a.eps);
+      sred[SRED_MEAN + threadIdx.x] = mean;
     }
     lds_barrier();
 #pragma unroll
     for (int j = 0; j < MT; ++j) {
-      sc[j] = sred[768 + j * 16 + (lane & 15)];
-      mu[j] = sred[896 + j * 16 + (lane & 15)];
+      sc[j] = sred[SRED_SCALE + j * 16 + (lane & 15)];
+      mu[j] = sred[SRED_MEAN + j * 16 + (lane & 15)];
     }
     lds_barrier();
   }
 
-  float4v_ acc[RT][MT];
+  float4v acc[RT][MT];
 #pragma unroll
   for (int i = 0; i < RT; ++i)
 #pragma unroll
-    for (int j = 0; j < MT; ++j) acc[i][j] = (float4v_){0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < MT; ++j) acc[i][j] = (float4v){0.f, 0.f, 0.f, 0.f};
   if constexpr (XL) {
     stream_k_xl(w0, w1, xr, acc, wp, tile_stride, a.x, a.ldx, xs, ks0, ng, lane);
-    if constexpr (MODE == EPI_ROPE && !EARLY_EPI) load_rope_ops();
+    if constexpr (MODE == FEPI_ROPE && !EARLY_EPI) load_rope_ops();
   } else {
-    stream_k(f0, f1, acc, wp, tile_stride, xp, a.ldx, ks0, ng, rot);
+    stream_k(f0, f1, acc, wp, tile_stride, xp, a.ldx, ks0, ng);
   }
 
   if constexpr (WK > 1) {
@@ -747,7 +746,7 @@ __device__ __forceinline__ void skinny_fused_tile(const FusedArgs& a, float* sme
 #pragma unroll
         for (int j = 0; j < MT; ++j)
           __builtin_amdgcn_raw_buffer_store_b128(
-              __builtin_bit_cast(u32x4_, acc[i][j]), rsrc,
+              __builtin_bit_cast(u32x4, acc[i][j]), rsrc,
               (((slab0 + s * RT * MT) + i * MT + j) * 64 + lane) * 16, 0, 16);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
@@ -774,16 +773,16 @@ __device__ __forceinline__ void skinny_fused_tile(const FusedArgs& a, float* sme
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     // fixed summation order (split 0..S-1) whichever block arrives last
-    float4v_ tot[RT][MT];
+    float4v tot[RT][MT];
 #pragma unroll
     for (int i = 0; i < RT; ++i)
 #pragma unroll
-      for (int j = 0; j < MT; ++j) tot[i][j] = float4v_{0.f, 0.f, 0.f, 0.f};
+      for (int j = 0; j < MT; ++j) tot[i][j] = float4v{0.f, 0.f, 0.f, 0.f};
     // QB slabs per batch, every load issued before the adds (a rolled loop
     // pays one L2 round trip per split); out-of-range slots add exact zeros
     constexpr int QB = (8 / (RT * MT)) > 2 ? 8 / (RT * MT) : 2;
     for (int q0 = 0; q0 < a.S; q0 += QB) {
-      float4v_ v[QB][RT][MT];
+      float4v v[QB][RT][MT];
 #pragma unroll
       for (int qq = 0; qq < QB; ++qq)
 #pragma unroll
@@ -791,9 +790,9 @@ __device__ __forceinline__ void skinny_fused_tile(const FusedArgs& a, float* sme
 #pragma unroll
           for (int j = 0; j < MT; ++j)
             v[qq][i][j] = q0 + qq < a.S
-                              ? __builtin_bit_cast(float4v_, __builtin_amdgcn_raw_buffer_load_b128(
+                              ? __builtin_bit_cast(float4v, __builtin_amdgcn_raw_buffer_load_b128(
                                                                  rsrc, (((slab0 + (q0 + qq) * RT * MT) + i * MT + j) * 64 + lane) * 16, 0, 16))
-                              : float4v_{0.f, 0.f, 0.f, 0.f};
+                              : float4v{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int qq = 0; qq < QB; ++qq)
 #pragma unroll
@@ -854,7 +853,7 @@ __device__ __forceinline__ void skinny_fused_tile(const FusedArgs& a, float* sme
       }
     }
   }
-  if constexpr (MODE == EPI_SILU) {
+  if constexpr (MODE == FEPI_SILU) {
     // 16-row pair tiles (perm_gate_up): rows 0-7 gate, rows 8-15 the matching
     // up rows -> lane l (l < 32) holds gate, lane l ^ 32 its up partner
 #pragma unroll
@@ -876,7 +875,7 @@ __device__ __forceinline__ void skinny_fused_tile(const FusedArgs& a, float* sme
           *reinterpret_cast<uint2*>(a.out + (size_t)m * a.ldo + (tile * RT + i) * 8 + nq) = w2;
         }
       }
-  } else if constexpr (MODE == EPI_RESID) {
+  } else if constexpr (MODE == FEPI_RESID) {
 #pragma unroll
     for (int j = 0; j < MT; ++j) {
       const int m = j * 16 + (lane & 15);
@@ -905,7 +904,7 @@ __device__ __forceinline__ void skinny_fused_tile(const FusedArgs& a, float* sme
         if (a.rowsum_out) a.rowsum_out[(size_t)tile * a.Mpad + m] = sm;
       }
     }
-  } else if constexpr (MODE == EPI_ROPE) {
+  } else if constexpr (MODE == FEPI_ROPE) {
     // perm_rope_qkv: q / k as 16-row pair tiles (rows 0-7 = first-half features
     // c.., rows 8-15 = partners c+D/2..: lane l and l ^ 32 hold a RoPE pair);
     // v rows in natural order
@@ -960,7 +959,7 @@ __device__ __forceinline__ void skinny_fused_tile(const FusedArgs& a, float* sme
         }
       }
     }
-  } else if constexpr (MODE == EPI_ACT) {
+  } else if constexpr (MODE == FEPI_ACT) {
     if (a.act == 2) {
       // f32 output (tensor-parallel partial sums: the all-reduce adds them in
       // f32 before the one bf16 rounding of the residual, as the single-GPU
@@ -1023,103 +1022,82 @@ static void launch_fused_kernel(dim3 grid, const FusedArgs& a, hipStream_t st) {
     hipLaunchKernelGGL((skinny_fused_kernel<RT, MT, U, WR, MODE, NORM, XL>), grid, dim3(256), 0, st, a);
 }
 
-// Prefetch groups of 4 k-steps, of 2 or 1 when the wave's k range does not
-// divide. (Deeper groups - 8 steps, or a Whisper wave's whole 10-step range
-// in one - measured slower in the pipeline, 3.51 -> 3.68 ms per LLM step, and
-// were removed: docs/KNOBS.md.)
+// One layout (RT, MT, WR, XL) -> its kernel, by the prefetch group U.
+// WR = 1 (4 waves along K): groups of 4 k-steps, of 2 or 1 when the wave's k
+// range does not divide. (Deeper groups - 8 steps, or a Whisper wave's whole
+// 10-step range in one - measured slower in the pipeline, 3.51 -> 3.68 ms per
+// LLM step, and were removed: docs/KNOBS.md.)
 // (fp8: a 16-byte weight load spans two k-steps, so a wave's k range must be
 // even - K % (S * WK * 64) == 0 - and is rejected otherwise)
-template <int RT, int MT, int WR, int MODE, int NORM, int FP8 = 0>
+// WR = 4: one group size per layout. loqa_skinny_fused admits only
+// K % (S * 128) == 0, and WR = 4 without XL only S == 1, so a wave's k range
+// is a multiple of 4 k-steps and no smaller group is ever needed; the check
+// here keeps a caller that bypasses the entry point from reading past K.
+//   register form: at most 2 k-steps per group at Mpad 64 (VGPRs);
+//   XL: the group is one LDS chunk, 2 k-steps when the VGPR budget is tight.
+template <int RT, int MT, int WR, int XL, int MODE, int NORM, int FP8>
 static int launch_fused(const FusedArgs& a, hipStream_t st) {
   constexpr int WK = 4 / WR;
   dim3 grid(a.N / (16 * RT * WR), a.S);
   const int kw = a.K / 32 / (a.S * WK);
-  if (MT <= 2 && kw % 4 == 0)   // Mpad 64: at most 2 k-steps per prefetch group (VGPRs)
-    launch_fused_kernel<FP8, RT, MT, (MT <= 2 ? 4 : 2), WR, MODE, NORM, 0>(grid, a, st);
-  else if (kw % 2 == 0)
-    launch_fused_kernel<FP8, RT, MT, 2, WR, MODE, NORM, 0>(grid, a, st);
-  else if constexpr (!FP8)
-    launch_fused_kernel<0, RT, MT, 1, WR, MODE, NORM, 0>(grid, a, st);
-  else
+  if constexpr (WR == 4) {
+    constexpr int U = XL ? (RT * MT >= 16 ? 2 : 4) : (MT <= 2 ? 4 : 2);
+    if (kw % U) return (int)hipErrorInvalidValue;
+    launch_fused_kernel<FP8, RT, MT, U, 4, MODE, NORM, XL>(grid, a, st);
+  } else if (MT <= 2 && kw % 4 == 0) {   // Mpad 64: at most 2 k-steps per prefetch group (VGPRs)
+    launch_fused_kernel<FP8, RT, MT, (MT <= 2 ? 4 : 2), 1, MODE, NORM, 0>(grid, a, st);
+  } else if (kw % 2 == 0) {
+    launch_fused_kernel<FP8, RT, MT, 2, 1, MODE, NORM, 0>(grid, a, st);
+  } else if constexpr (!FP8) {
+    launch_fused_kernel<0, RT, MT, 1, 1, MODE, NORM, 0>(grid, a, st);
+  } else {
     return (int)hipErrorInvalidValue;
-  return (int)hipGetLastError();
-}
-
-template <int RT, int MODE, int NORM, int FP8>
-static int dispatch_mt(const FusedArgs& a, int wr, hipStream_t st) {
-  switch (a.Mpad) {
-    case 16:
-      if (wr == 4) return launch_fused<RT, 1, 4, MODE, NORM, FP8>(a, st);
-      return launch_fused<RT, 1, 1, MODE, NORM, FP8>(a, st);
-    case 32:
-      if (wr == 4) return launch_fused<RT, 2, 4, MODE, NORM, FP8>(a, st);
-      return launch_fused<RT, 2, 1, MODE, NORM, FP8>(a, st);
-    default:
-      if (wr == 4) return launch_fused<RT, 4, 4, MODE, NORM, FP8>(a, st);
-      return launch_fused<RT, 4, 1, MODE, NORM, FP8>(a, st);
   }
-}
-
-// XL dispatch: Mpad 32 (MT 2) / 64 (MT 4) / 128 (MT 8), 4 waves along rows, any split-K.
-// Prefetch group = one LDS chunk: 4 k-steps, 2 when the VGPR budget is tight.
-template <int RT, int MT, int MODE, int NORM, int FP8>
-static int launch_xl(const FusedArgs& a, hipStream_t st) {
-  dim3 grid(a.N / (16 * RT * 4), a.S);
-  const int kw = a.K / 32 / a.S;
-  constexpr int UA = (RT * MT >= 16) ? 2 : 4;
-  if (kw % UA == 0)
-    launch_fused_kernel<FP8, RT, MT, UA, 4, MODE, NORM, 1>(grid, a, st);
-  else if (kw % 2 == 0)
-    launch_fused_kernel<FP8, RT, MT, 2, 4, MODE, NORM, 1>(grid, a, st);
-  else if constexpr (MT * 16 * 4 >= 256 && !FP8)   // a 1-k-step x chunk must cover the 256 threads' pieces
-    launch_fused_kernel<0, RT, MT, 1, 4, MODE, NORM, 1>(grid, a, st);
-  else
-    return (int)hipErrorInvalidValue;
   return (int)hipGetLastError();
 }
 
-template <int MODE, int NORM, int FP8>
-static int dispatch_xl(const FusedArgs& a, int rt, hipStream_t st) {
-  if (a.Mpad == 32)
-    return rt == 2 ? launch_xl<2, 2, MODE, NORM, FP8>(a, st) : launch_xl<1, 2, MODE, NORM, FP8>(a, st);
-  if (a.Mpad == 64)
-    return rt == 2 ? launch_xl<2, 4, MODE, NORM, FP8>(a, st) : launch_xl<1, 4, MODE, NORM, FP8>(a, st);
-  return rt == 2 ? launch_xl<2, 8, MODE, NORM, FP8>(a, st) : launch_xl<1, 8, MODE, NORM, FP8>(a, st);
-}
-
+// Every legal layout, as (Mpad, rt, wr, xl) -> launch_fused<RT, MT = Mpad / 16, WR, XL>.
 // rt: rows per output tile / 16 (1 or 2, every mode: the paired epilogues pair
 // rows inside each 16-row tile through a lane shuffle, so 16-row tiles give
 // twice the workgroups without a K split, i.e. without a reduction tail).
-// wr: waves along the rows (1 or 4; 4 only with S == 1).
+// rt 4: 64-row tiles at Mpad 64 (chunked prefill through the compact weights):
+// the activation tile is then re-read from L2 by half as many workgroups.
+// wr: waves along the rows (1 or 4; 4 only with S == 1, or with xl).
+// xl: x through LDS, Mpad 32 / 64 / 128, 4 waves along rows, any split-K.
 template <int MODE, int NORM, int FP8>
-static int dispatch_fused(const FusedArgs& a, int rt, int wr, hipStream_t st) {
-  // 64-row tiles at Mpad 64 (chunked prefill through the compact weights):
-  // the activation tile is then re-read from L2 by half as many workgroups
-  if (rt == 4) {
-    if (wr == 4) return launch_fused<4, 4, 4, MODE, NORM, FP8>(a, st);
-    return launch_fused<4, 4, 1, MODE, NORM, FP8>(a, st);
-  }
-  if (rt == 1) return dispatch_mt<1, MODE, NORM, FP8>(a, wr, st);
-  return dispatch_mt<2, MODE, NORM, FP8>(a, wr, st);
+static int dispatch_shape(const FusedArgs& a, int rt, int wr, int xl, hipStream_t st) {
+  auto is = [&](int mpad, int r, int w, int x) { return a.Mpad == mpad && rt == r && wr == w && !xl == !x; };
+  if (is(16, 1, 1, 0)) return launch_fused<1, 1, 1, 0, MODE, NORM, FP8>(a, st);
+  if (is(16, 1, 4, 0)) return launch_fused<1, 1, 4, 0, MODE, NORM, FP8>(a, st);
+  if (is(16, 2, 1, 0)) return launch_fused<2, 1, 1, 0, MODE, NORM, FP8>(a, st);
+  if (is(16, 2, 4, 0)) return launch_fused<2, 1, 4, 0, MODE, NORM, FP8>(a, st);
+  if (is(32, 1, 1, 0)) return launch_fused<1, 2, 1, 0, MODE, NORM, FP8>(a, st);
+  if (is(32, 1, 4, 0)) return launch_fused<1, 2, 4, 0, MODE, NORM, FP8>(a, st);
+  if (is(32, 2, 1, 0)) return launch_fused<2, 2, 1, 0, MODE, NORM, FP8>(a, st);
+  if (is(32, 2, 4, 0)) return launch_fused<2, 2, 4, 0, MODE, NORM, FP8>(a, st);
+  if (is(64, 1, 1, 0)) return launch_fused<1, 4, 1, 0, MODE, NORM, FP8>(a, st);
+  if (is(64, 1, 4, 0)) return launch_fused<1, 4, 4, 0, MODE, NORM, FP8>(a, st);
+  if (is(64, 2, 1, 0)) return launch_fused<2, 4, 1, 0, MODE, NORM, FP8>(a, st);
+  if (is(64, 2, 4, 0)) return launch_fused<2, 4, 4, 0, MODE, NORM, FP8>(a, st);
+  if (is(64, 4, 1, 0)) return launch_fused<4, 4, 1, 0, MODE, NORM, FP8>(a, st);
+  if (is(64, 4, 4, 0)) return launch_fused<4, 4, 4, 0, MODE, NORM, FP8>(a, st);
+  if (is(32, 1, 4, 1)) return launch_fused<1, 2, 4, 1, MODE, NORM, FP8>(a, st);
+  if (is(32, 2, 4, 1)) return launch_fused<2, 2, 4, 1, MODE, NORM, FP8>(a, st);
+  if (is(64, 1, 4, 1)) return launch_fused<1, 4, 4, 1, MODE, NORM, FP8>(a, st);
+  if (is(64, 2, 4, 1)) return launch_fused<2, 4, 4, 1, MODE, NORM, FP8>(a, st);
+  if (is(128, 1, 4, 1)) return launch_fused<1, 8, 4, 1, MODE, NORM, FP8>(a, st);
+  if (is(128, 2, 4, 1)) return launch_fused<2, 8, 4, 1, MODE, NORM, FP8>(a, st);
+  return (int)hipErrorInvalidValue;
 }
 
 // fp8 weights: NORM_NONE and NORM_RMS only (the Llama decode), LayerNorm is rejected
 template <int MODE, int FP8>
 static int dispatch_norm(const FusedArgs& a, int norm, int rt, int wr, int xl, hipStream_t st) {
-  if (xl) {
-    switch (norm) {
-      case NORM_NONE: return dispatch_xl<MODE, NORM_NONE, FP8>(a, rt, st);
-      case NORM_RMS: return dispatch_xl<MODE, NORM_RMS, FP8>(a, rt, st);
-      case NORM_LN:
-        if constexpr (!FP8) return dispatch_xl<MODE, NORM_LN, 0>(a, rt, st);
-      default: return (int)hipErrorInvalidValue;
-    }
-  }
   switch (norm) {
-    case NORM_NONE: return dispatch_fused<MODE, NORM_NONE, FP8>(a, rt, wr, st);
-    case NORM_RMS: return dispatch_fused<MODE, NORM_RMS, FP8>(a, rt, wr, st);
+    case NORM_NONE: return dispatch_shape<MODE, NORM_NONE, FP8>(a, rt, wr, xl, st);
+    case NORM_RMS: return dispatch_shape<MODE, NORM_RMS, FP8>(a, rt, wr, xl, st);
     case NORM_LN:
-      if constexpr (!FP8) return dispatch_fused<MODE, NORM_LN, 0>(a, rt, wr, st);
+      if constexpr (!FP8) return dispatch_shape<MODE, NORM_LN, 0>(a, rt, wr, xl, st);
     default: return (int)hipErrorInvalidValue;
   }
 }
@@ -1127,11 +1105,10 @@ static int dispatch_norm(const FusedArgs& a, int norm, int rt, int wr, int xl, h
 template <int FP8>
 static int dispatch_mode(const FusedArgs& a, int mode, int norm, int rt, int wr, int xl, hipStream_t st) {
   switch (mode) {
-    case EPI_SILU: return dispatch_norm<EPI_SILU, FP8>(a, norm, rt, wr, xl, st);
-    case EPI_RESID: return dispatch_norm<EPI_RESID, FP8>(a, norm, rt, wr, xl, st);
-    case EPI_ROPE: return dispatch_norm<EPI_ROPE, FP8>(a, norm, rt, wr, xl, st);
-    case EPI_ACT: return dispatch_norm<EPI_ACT, FP8>(a, norm, rt, wr, xl, st);
+    case FEPI_SILU: return dispatch_norm<FEPI_SILU, FP8>(a, norm, rt, wr, xl, st);
+    case FEPI_RESID: return dispatch_norm<FEPI_RESID, FP8>(a, norm, rt, wr, xl, st);
+    case FEPI_ROPE: return dispatch_norm<FEPI_ROPE, FP8>(a, norm, rt, wr, xl, st);
+    case FEPI_ACT: return dispatch_norm<FEPI_ACT, FP8>(a, norm, rt, wr, xl, st);
     default: return (int)hipErrorInvalidValue;
   }
 }
-

@@ -9,22 +9,7 @@
 extern "C" int loqa_skinny_gemm(const void* x, long long ldx_, const void* Wp, float* part, int Mpad,
                                 int N, int K, int S, int max_wgs, hipStream_t st) {
   if (S < 1 || K % (S * 4 * 32) != 0 || ldx_ % 8 != 0 || N % 16 != 0) return (int)hipErrorInvalidValue;
-  switch (Mpad) {
-    case 16:
-      if (N % 32) return (int)hipErrorInvalidValue;
-      return launch_skinny<2, 1>(x, ldx_, Wp, part, N, K, S, Mpad, max_wgs, st);
-    case 32:
-      if (N % 32) return (int)hipErrorInvalidValue;
-      return launch_skinny<2, 2>(x, ldx_, Wp, part, N, K, S, Mpad, max_wgs, st);
-    case 64:
-      if (N % 64) return (int)hipErrorInvalidValue;
-      return launch_skinny<4, 4>(x, ldx_, Wp, part, N, K, S, Mpad, max_wgs, st);
-    case 128:
-      if (N % 64) return (int)hipErrorInvalidValue;
-      return launch_skinny<4, 8>(x, ldx_, Wp, part, N, K, S, Mpad, max_wgs, st);
-    default:
-      return (int)hipErrorInvalidValue;
-  }
+  return dispatch_skinny<bf16_t>(SkinnyArgs{x, ldx_, Wp, nullptr, part, N, K, S, Mpad, max_wgs}, st);
 }
 
 // W [N, K] row-major -> Wp[N/16][K/32][64][8] (fragment order of the kernel above)
@@ -54,8 +39,41 @@ extern "C" int loqa_shuffle_weight(const void* W, void* Wp, int N, int K, hipStr
   return (int)hipGetLastError();
 }
 
-// the ctypes mirror is held to this (tests/test_gemm_shared.py)
+// the ctypes mirror is held to these two (tests/test_gemm_shared.py): the size,
+// and the offset of every field in declaration order (returns the field count;
+// writes at most cap offsets)
 extern "C" int loqa_skinny_fused_params_size() { return (int)sizeof(FusedParams); }
+
+extern "C" int loqa_skinny_fused_params_offsets(int* out, int cap) {
+#define F(f) (int)offsetof(FusedParams, f)
+  const int off[] = {F(x), F(ldx), F(Wp), F(part), F(counters), F(Mpad), F(N), F(K), F(S), F(mode),
+                     F(norm), F(rowsq_in), F(rowsum_in), F(rowstat_tiles), F(eps), F(colsum), F(bias),
+                     F(out), F(ldo), F(act), F(residual), F(rowsq_out), F(rowsum_out), F(positions),
+                     F(cs), F(q_out), F(kc), F(vc), F(slots), F(H), F(Hkv), F(D), F(blk), F(rt), F(wr),
+                     F(xl), F(wdtype), F(wscale)};
+#undef F
+  const int n = (int)(sizeof(off) / sizeof(off[0]));
+  for (int i = 0; i < n && i < cap; ++i) out[i] = off[i];
+  return n;
+}
+
+// The kernel argument of a checked parameter block. (FusedArgs' field order is
+// the kernel-argument layout the kernels were measured with: it stays.)
+static FusedArgs fused_args(const FusedParams& p) {
+  FusedArgs a{};
+  a.x = (const bf16_t*)p.x, a.ldx = p.ldx, a.Wp = (const bf16_t*)p.Wp, a.wscale = p.wscale;
+  a.part = p.part, a.counters = p.counters;
+  a.N = p.N, a.K = p.K, a.S = p.S, a.Mpad = p.Mpad;
+  a.rowsq_in = p.rowsq_in, a.rowsum_in = p.rowsum_in, a.rowstat_tiles = p.rowstat_tiles, a.eps = p.eps;
+  a.colsum = p.colsum, a.bias = p.bias;
+  a.out = (bf16_t*)p.out, a.ldo = p.ldo, a.act = p.act;
+  a.residual = (bf16_t*)p.residual, a.rowsq_out = p.rowsq_out, a.rowsum_out = p.rowsum_out;
+  a.positions = p.positions, a.cs = (const float2*)p.cs, a.slots = p.slots;
+  a.q_out = (bf16_t*)p.q_out, a.kc = (bf16_t*)p.kc, a.vc = (bf16_t*)p.vc;
+  a.H = p.H, a.Hkv = p.Hkv, a.D = p.D, a.blk = p.blk;
+  a.prio = g_loqa_launch_prio;
+  return a;
+}
 
 // the fp8 weight stream's instances (gemm_skinny_fp8.hip)
 int loqa_skinny_fused_fp8_launch(const FusedArgs& a, int mode, int norm, int rt, int wr, int xl,
@@ -81,25 +99,19 @@ extern "C" int loqa_skinny_fused(const FusedParams* p, hipStream_t st) {
   if (S > 1 && (!p->part || !p->counters)) return (int)hipErrorInvalidValue;
   if (p->norm && (!p->rowsq_in || p->rowstat_tiles < 1)) return (int)hipErrorInvalidValue;
   if (p->norm == NORM_LN && (!p->rowsum_in || !p->colsum)) return (int)hipErrorInvalidValue;
-  if (p->mode == EPI_ROPE && (p->D % 16 || N != (p->H + 2 * p->Hkv) * p->D))
+  if (p->mode == FEPI_ROPE && (p->D % 16 || N != (p->H + 2 * p->Hkv) * p->D))
     return (int)hipErrorInvalidValue;
-  if ((p->mode == EPI_SILU || p->mode == EPI_ACT) && (!p->out || p->ldo % 4))
+  if ((p->mode == FEPI_SILU || p->mode == FEPI_ACT) && (!p->out || p->ldo % 4))
     return (int)hipErrorInvalidValue;
   if (p->rt != 1 && p->rt != 2 && !(p->rt == 4 && Mpad == 64)) return (int)hipErrorInvalidValue;
-  if (p->mode == EPI_RESID && (!p->residual || !p->rowsq_out)) return (int)hipErrorInvalidValue;
+  if (p->mode == FEPI_RESID && (!p->residual || !p->rowsq_out)) return (int)hipErrorInvalidValue;
   if (p->wr != 1 && (p->wr != 4 || (S != 1 && !p->xl) || N % (64 * p->rt)))
     return (int)hipErrorInvalidValue;
   if (p->wdtype != 0 && p->wdtype != 1) return (int)hipErrorInvalidValue;
   if (p->wdtype == 1 &&
       (!p->wscale || p->norm == NORM_LN || K % (S * (p->wr == 4 ? 1 : 4) * 64)))
     return (int)hipErrorInvalidValue;
-  FusedArgs a{(const bf16_t*)p->x, p->ldx, (const bf16_t*)p->Wp, p->part, N, K, S, Mpad,
-              p->counters, p->rowsq_in, p->rowsum_in, p->rowstat_tiles, p->eps, p->colsum,
-              p->bias, (bf16_t*)p->out, p->ldo, p->act, (bf16_t*)p->residual, p->rowsq_out,
-              p->rowsum_out, p->positions, (const float2*)p->cs, (bf16_t*)p->q_out,
-              (bf16_t*)p->kc, (bf16_t*)p->vc, p->slots, p->H, p->Hkv, p->D, p->blk};
-  a.prio = g_loqa_launch_prio;
-  a.wscale = p->wscale;
+  const FusedArgs a = fused_args(*p);
   if (p->wdtype == 1)
     return loqa_skinny_fused_fp8_launch(a, p->mode, p->norm, p->rt, p->wr, p->xl, st);
   return dispatch_mode<0>(a, p->mode, p->norm, p->rt, p->wr, p->xl, st);

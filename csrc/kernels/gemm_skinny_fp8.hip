@@ -21,20 +21,5 @@ extern "C" int loqa_skinny_gemm_fp8(const void* x, long long ldx_, const void* W
                                     hipStream_t st) {
   if (S < 1 || K % (S * 4 * 64) != 0 || ldx_ % 8 != 0 || N % 16 != 0 || !wscale)
     return (int)hipErrorInvalidValue;
-  switch (Mpad) {
-    case 16:
-      if (N % 32) return (int)hipErrorInvalidValue;
-      return launch_skinny_fp8<2, 1>(x, ldx_, Wp8, wscale, part, N, K, S, Mpad, max_wgs, st);
-    case 32:
-      if (N % 32) return (int)hipErrorInvalidValue;
-      return launch_skinny_fp8<2, 2>(x, ldx_, Wp8, wscale, part, N, K, S, Mpad, max_wgs, st);
-    case 64:
-      if (N % 64) return (int)hipErrorInvalidValue;
-      return launch_skinny_fp8<4, 4>(x, ldx_, Wp8, wscale, part, N, K, S, Mpad, max_wgs, st);
-    case 128:
-      if (N % 64) return (int)hipErrorInvalidValue;
-      return launch_skinny_fp8<4, 8>(x, ldx_, Wp8, wscale, part, N, K, S, Mpad, max_wgs, st);
-    default:
-      return (int)hipErrorInvalidValue;
-  }
+  return dispatch_skinny<fp8_t>(SkinnyArgs{x, ldx_, Wp8, wscale, part, N, K, S, Mpad, max_wgs}, st);
 }

@@ -109,6 +109,7 @@ _KERNEL_SIGS = {
     "loqa_shuffle_weight": [c_void_p, c_void_p, c_int, c_int, c_void_p],
     "loqa_skinny_fused": [c_void_p, c_void_p],
     "loqa_skinny_fused_params_size": [],
+    "loqa_skinny_fused_params_offsets": [c_void_p, c_int],
     "loqa_gemm_tile":[c_void_p, c_void_p],
     "loqa_gemm_tile_dims": [c_int, c_void_p, c_void_p],
     "loqa_gemm_sk": [c_void_p, c_void_p],

@@ -197,7 +197,7 @@ def _rejected(e: RuntimeError) -> bool:
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("K", [1024, 1536])
+@pytest.mark.parametrize("K", [256, 768, 1024, 1536])
 @pytest.mark.parametrize("norm", [None, "rms"])
 @pytest.mark.parametrize("mode", ["resid", "silu", "act", "rope"])
 def test_fp8_fused_bitwise_vs_bf16_kernel_gpu(mode, norm, K):
@@ -205,7 +205,11 @@ def test_fp8_fused_bitwise_vs_bf16_kernel_gpu(mode, norm, K):
     on the (exactly) dequantised weights, same layout: bitwise equal, every
     output. K = 1536: an odd number of prefetch groups per wave (the ping-pong
     tail). A layout is skipped only when the host dispatch rejects it for fp8
-    at this K; at most two of the eight."""
+    at this K; at most two of the eight.
+    K = 256 and 768: with 4 waves along K the fp8 stream's two-k-step group, in
+    one and in three groups. These K do not divide by every layout's split, so
+    they run the layouts the entry checks take (K % (S * 128) == 0 and, fp8,
+    K % (S * waves-along-K * 64) == 0) and none of those may be rejected."""
     if norm and mode == "resid":
         pytest.skip("no residual GEMM takes a norm prologue (it would rewrite the statistics it reads)")
     dev = "cuda"
@@ -217,7 +221,11 @@ def test_fp8_fused_bitwise_vs_bf16_kernel_gpu(mode, norm, K):
     g = torch.Generator().manual_seed(5)
     cs = ref.rope_cos_sin(D, 512, 10000.0)
     skipped = []
-    for Mpad, rt, wr, S, xl in LAYOUTS:
+    layouts = LAYOUTS
+    if K < 1024:
+        layouts = [l for l in LAYOUTS if K % (l[3] * 128) == 0 and K % (l[3] * (1 if l[2] == 4 else 4) * 64) == 0]
+        assert (16, 1, 1, 1, 0) in layouts and len(layouts) >= 5
+    for Mpad, rt, wr, S, xl in layouts:
         x = torch.randn(Mpad, K, generator=g).bfloat16()
         res0 = torch.randn(Mpad, N, generator=g).bfloat16()
         rowsq = torch.rand(4 * Mpad, generator=g) * 300 + 50
@@ -225,7 +233,7 @@ def test_fp8_fused_bitwise_vs_bf16_kernel_gpu(mode, norm, K):
         try:
             got = _run_fused(dev, w8, *args)
         except RuntimeError as e:
-            if not _rejected(e):
+            if not _rejected(e) or K < 1024:
                 raise
             skipped.append((Mpad, rt, wr, S, xl))
             continue
@@ -253,18 +261,22 @@ def test_fp8_fused_act_f32_bitwise_gpu():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("K", [1024, 1536])
+@pytest.mark.parametrize("K", [256, 768, 1024, 1536])
 @pytest.mark.parametrize("Mpad", [16, 64])
 def test_fp8_skinny_gemm_bitwise_vs_bf16_kernel_gpu(Mpad, K):
     """The lm_head form: slabs bitwise equal to the bf16 kernel's; N = 576
-    padded to 640 with zero rows (scale 1), whose outputs are exactly 0."""
+    padded to 640 with zero rows (scale 1), whose outputs are exactly 0.
+    K = 256, 768: a wave's two-k-step group in one and in three groups (S = 1;
+    S = 2 only where K % (S * 4 * 64) == 0, the fp8 entry check)."""
     dev, N, Np = "cuda", 576, 640
     q, scale = _exact_weights(Np, K, seed=13, zero_from=N)
     scale[N:] = 1.0
     w8 = _fp8_from(q, scale, dev)
     wb = ops.shuffle_weight((q.float() * scale[:, None]).bfloat16().to(dev))
     x = torch.randn(Mpad, K).bfloat16().to(dev)
-    for S in (1, 2):
+    splits = [S for S in (1, 2) if K % (S * 4 * 64) == 0]
+    assert 1 in splits and (K < 1024 or splits == [1, 2])
+    for S in splits:
         a, b = ops.skinny_gemm(x, w8, S), ops.skinny_gemm(x, wb, S)
         assert a.shape == (S, Mpad, Np) and torch.equal(a, b)
         assert not a[:, :, N:].any()

@@ -314,3 +314,121 @@ def test_fused_scratch_holds_70b_mpad128():
     scr = ops.FusedScratch(torch.device("cpu"))
     ntiles = 57344 // 16
     assert ntiles <= scr.counters.numel() and ntiles * 128 <= scr.rowsq.numel()
+
+
+# ---- exact checks of the bf16 weight stream -------------------------------
+# Integer-valued bf16 inputs from {-2, -1, 1, 2} (no zeros): every product and
+# every partial sum over K <= 2048 is an integer of magnitude <= 4 * 2048 <
+# 2^24, so f32 accumulation is exact in any order and the f32 output must EQUAL
+# x @ w^T whatever the layout, the prefetch group and the split. A k-step that
+# is skipped, read twice or read from the wrong place changes the result (the
+# CPU test below shows that for every k-step of every K).
+# With 4 waves along K (wr = 1, S = 1) the K list gives a wave 1, 2, 3, 4, 5,
+# 6, 8, 12 and 16 k-steps: prefetch groups of 1 k-step in 1, 3 and 5 groups,
+# of 2 in 1, 2, 3, 4, 6 and 8, of 4 in 1, 2, 3 and 4 - every branch of
+# stream_k and stream_k_xl (one group, odd and even group counts).
+EXACT_KS = (128, 256, 384, 512, 640, 768, 1024, 1536, 2048)
+# (Mpad, rt, wr, xl)
+EXACT_LAYOUTS = ((16, 1, 1, 0), (16, 2, 1, 0), (16, 2, 4, 0), (64, 2, 1, 0), (64, 4, 4, 0), (32, 1, 4, 1),
+                 (128, 2, 4, 1))
+_EXACT = {}
+
+
+def _exact_inputs():
+    """x [128, 2048], w [256, 2048] (cases take leading slices) and, per K, the
+    f32 product of the slices; built once, never written."""
+    if not _EXACT:
+        g = torch.Generator().manual_seed(11)
+        vals = torch.tensor([-2.0, -1.0, 1.0, 2.0])
+        x = vals[torch.randint(0, 4, (128, 2048), generator=g)].bfloat16()
+        w = vals[torch.randint(0, 4, (256, 2048), generator=g)].bfloat16()
+        _EXACT.update(x=x, w=w, ref={K: x[:, :K].float() @ w[:, :K].float().t() for K in EXACT_KS})
+    return _EXACT
+
+
+def _exact_n(rt, wr):
+    """N = 128, or the smallest N the layout takes: 4 waves along rows need
+    N % (64 * rt) == 0 (loqa_skinny_fused), i.e. 256 for the 64-row tiles."""
+    return 128 if wr == 1 or 128 % (64 * rt) == 0 else 64 * rt
+
+
+def _exact_allowed(K, S, wr, xl):
+    """loqa_skinny_fused's checks on (K, S, wr, xl) for bf16 weights."""
+    return K % (S * 128) == 0 and (wr == 1 or S == 1 or bool(xl))
+
+
+def _nan_strided(x, dev):
+    """x as a strided view into a larger NaN-filled buffer."""
+    M, K = x.shape
+    buf = torch.full((M + 2, K + 16), float("nan"), dtype=torch.bfloat16, device=dev)
+    view = buf[1:1 + M, 8:8 + K]
+    view.copy_(x)
+    return view
+
+
+def test_exact_inputs_can_fail_cpu():
+    """The exact tests' inputs notice every k-step: for every K, zeroing any one
+    32-wide k-step of w changes at least one output element, and so does
+    adding any one k-step a second time."""
+    e = _exact_inputs()
+    for K in EXACT_KS:
+        x, w, want = e["x"][:16, :K].float(), e["w"][:128, :K].float(), e["ref"][K][:16, :128]
+        assert torch.equal(x @ w.t(), want)
+        assert not (x == 0).any() and not (w == 0).any()
+        for ks in range(K // 32):
+            sl = slice(ks * 32, ks * 32 + 32)
+            wz = w.clone()
+            wz[:, sl] = 0
+            assert not torch.equal(x @ wz.t(), want), (K, ks, "dropped")
+            twice = torch.cat([x, x[:, sl]], 1) @ torch.cat([w, w[:, sl]], 1).t()
+            assert not torch.equal(twice, want), (K, ks, "twice")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("Mpad,rt,wr,xl", EXACT_LAYOUTS)
+def test_fused_act_f32_exact_gpu(Mpad, rt, wr, xl):
+    """skinny_fused, mode "act" with f32 output, bitwise against x @ w^T for
+    every K of EXACT_KS and S = 1, 2 (where the entry checks allow the split),
+    the layout passed explicitly (the tuner never runs). x is a strided view
+    into a NaN-filled buffer; the output is a view into a sentinel-filled
+    buffer that is compared whole (nothing written outside the view)."""
+    e = _exact_inputs()
+    dev = torch.device("cuda", 0)
+    N = _exact_n(rt, wr)
+    scr = ops.FusedScratch(dev)
+    ran = 0
+    for K in EXACT_KS:
+        wp = ops.shuffle_weight(e["w"][:N, :K].contiguous().to(dev))
+        xd = _nan_strided(e["x"][:Mpad, :K], dev)
+        want = torch.full((Mpad + 2, N + 8), -77.0)
+        want[1:1 + Mpad, 4:4 + N] = e["ref"][K][:Mpad, :N]
+        for S in (1, 2):
+            if not _exact_allowed(K, S, wr, xl):
+                continue
+            buf = torch.full((Mpad + 2, N + 8), -77.0, dtype=torch.float32, device=dev)
+            ops.skinny_fused(xd, wp, "act", scr, splits=S, rt=rt, wr=wr, xl=xl, act="f32",
+                             out=buf[1:1 + Mpad, 4:4 + N])
+            assert torch.equal(buf.cpu(), want), (K, S)
+            ran += 1
+    assert ran >= len(EXACT_KS)        # S = 1 runs for every K
+    assert int(scr.counters.abs().sum()) == 0      # the split-K tickets are left at zero
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("Mpad", [16, 64])
+def test_skinny_gemm_exact_gpu(Mpad):
+    """The plain skinny GEMM: its split-K slabs, summed, equal x @ w^T bitwise
+    for every K of EXACT_KS (prefetch groups of 4 at Mpad 16, of 2 at Mpad 64, of
+    1 where a wave's k range is odd) with S = 1 and 2."""
+    e = _exact_inputs()
+    dev = torch.device("cuda", 0)
+    N = 128
+    for K in EXACT_KS:
+        wp = ops.shuffle_weight(e["w"][:N, :K].contiguous().to(dev))
+        xd = _nan_strided(e["x"][:Mpad, :K], dev)
+        for S in (1, 2):
+            if K % (S * 128):          # loqa_skinny_gemm's check
+                continue
+            part = ops.skinny_gemm(xd, wp, splits=S)
+            assert part.shape == (S, Mpad, N)
+            assert torch.equal(part.sum(0).cpu(), e["ref"][K][:Mpad, :N]), (K, S)

@@ -43,10 +43,17 @@ def test_layout_tables_match_the_kernels():
 
 def test_fused_params_mirror_has_the_kernels_size():
     """_lib.FusedParams is gemm_skinny.hip's FusedParams restated by hand: hold
-    its size to the exported sizeof (host-only call, no GPU work)."""
+    its size to the exported sizeof and the offset of every field, in
+    declaration order, to the exported offsetof list - two same-sized fields
+    swapped keep the size (host-only calls, no GPU work)."""
     if not _lib.available():
         pytest.skip("native kernels library not built")
-    assert ctypes.sizeof(_lib.FusedParams) == _lib.kernels().loqa_skinny_fused_params_size()
+    lib = _lib.kernels()
+    assert ctypes.sizeof(_lib.FusedParams) == lib.loqa_skinny_fused_params_size()
+    fields = [name for name, _ in _lib.FusedParams._fields_]
+    off = (ctypes.c_int * (len(fields) + 8))()
+    assert lib.loqa_skinny_fused_params_offsets(off, len(off)) == len(fields)
+    assert [getattr(_lib.FusedParams, f).offset for f in fields] == list(off[: len(fields)])
 
 
 @pytest.fixture(scope="module")

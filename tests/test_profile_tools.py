@@ -95,3 +95,77 @@ def test_kernel_summary_top_n(tmp_path):
     out = _run("scripts/kernel_summary.py", str(p), "1")
     assert out[0].startswith("total kernel time: 10.00 ms over 13 dispatches")
     assert len(out) == 3 and out[2].split()[-1] == "big"
+
+
+_ASM = """\t.text
+\t.protected\t_Z1kv
+\t.globl\t_Z1kv
+\t.p2align\t8
+\t.type\t_Z1kv,@function
+_Z1kv:                                  ; @_Z1kv
+; %bb.0:
+\ts_load_dwordx2 s[0:1], s[4:5], 0x0   ; a comment
+\tglobal_load_dwordx4 v[0:3], v4, s[0:1]
+\tglobal_load_dwordx4 v[6:9], v4, s[0:1] offset:16
+.LBB{fn}_1:
+\ts_waitcnt vmcnt({wait})
+\tv_mfma_f32_16x16x32_bf16 a[0:3], v[0:3], v[6:9], a[0:3]
+\tds_write_b128 v5, v[0:3]
+\ts_waitcnt lgkmcnt(0)
+\ts_barrier
+\tds_read_b128 v[0:3], v5
+\ts_cbranch_scc1 .LBB{fn}_1
+\ts_waitcnt vmcnt(0)
+\tglobal_store_dwordx4 v4, v[0:3], s[0:1]
+{extra}\ts_endpgm
+\t.section\t.rodata,"a",@progbits
+\t.p2align\t6, 0x0
+\t.amdhsa_kernel _Z1kv
+\t\t.amdhsa_next_free_vgpr {vgpr}
+\t\t.amdhsa_accum_offset {accum}
+\t.end_amdhsa_kernel
+\t.text
+.Lfunc_end{fn}:
+\t.size\t_Z1kv, .Lfunc_end{fn}-_Z1kv
+"""
+_RES = """k.hip:3:1: remark: Function Name: _Z1kv [-Rpass-analysis=kernel-resource-usage]
+k.hip:3:1: remark:     TotalSGPRs: 16 [-Rpass-analysis=kernel-resource-usage]
+k.hip:3:1: remark:     VGPRs: {vgpr} [-Rpass-analysis=kernel-resource-usage]
+k.hip:3:1: remark:     AGPRs: 4 [-Rpass-analysis=kernel-resource-usage]
+k.hip:3:1: remark:     ScratchSize [bytes/lane]: 0 [-Rpass-analysis=kernel-resource-usage]
+k.hip:3:1: remark:     Occupancy [waves/SIMD]: 8 [-Rpass-analysis=kernel-resource-usage]
+k.hip:3:1: remark:     SGPRs Spill: 0 [-Rpass-analysis=kernel-resource-usage]
+k.hip:3:1: remark:     VGPRs Spill: 0 [-Rpass-analysis=kernel-resource-usage]
+k.hip:3:1: remark:     LDS Size [bytes/block]: 1024 [-Rpass-analysis=kernel-resource-usage]
+"""
+
+
+def test_kernel_asm_diff_on_two_snippets(tmp_path):
+    """scripts/kernel_asm_diff.py on synthetic assembly: the same kernel under
+    another function number and with other comments is identical and passes; a
+    drained prefetch (vmcnt(1) -> vmcnt(0)), two more VGPRs and one more store
+    are each reported and fail the run."""
+    def put(tag, fn, wait, vgpr, extra=""):
+        s, r = tmp_path / f"{tag}.s", tmp_path / f"{tag}.res"
+        s.write_text(_ASM.format(fn=fn, wait=wait, vgpr=vgpr, accum=(vgpr + 3) // 4 * 4, extra=extra))
+        r.write_text(_RES.format(vgpr=vgpr))
+        return [str(s), str(r)]
+
+    def run(*files):
+        return subprocess.run([sys.executable, "scripts/kernel_asm_diff.py", *files, "--list"], cwd=ROOT,
+                              capture_output=True, text=True, timeout=60)
+
+    before = put("before", 0, 1, 10)
+    same = run(*before, *put("same", 7, 1, 10))
+    assert same.returncode == 0, same.stdout + same.stderr
+    assert "1 identical instruction text, 0 not" in same.stdout and "unchanged" in same.stdout
+    worse = run(*before, *put("worse", 0, 0, 12, "\tglobal_store_dword v4, v0, s[0:1]\n"))
+    assert worse.returncode == 1
+    out = worse.stdout
+    assert "0 identical instruction text, 1 not (instruction count +1 .. +1)" in out
+    assert "FAIL vmcnt(0) waits 1 -> 2: _Z1kv" in out
+    assert "FAIL vgpr 10 -> 12: _Z1kv" in out and "FAIL accum_offset 12 -> 12" not in out
+    assert "FAIL vstore count 1 -> 2: _Z1kv" in out
+    assert "mfma" not in out and "barrier" not in out       # equal counts are not reported
+    gone = run(*put("two", 0, 1, 10), str(tmp_path / "same.s"), str(tmp_path / "same.res"), "--removed-ok", "nomatch")
+    assert gone.returncode == 0 and "0 removed" in gone.stdout
