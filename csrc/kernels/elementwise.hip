@@ -456,6 +456,201 @@ extern "C" int loqa_masked_argmax(const void* logits, int is_bf16, long long ld,
   return (int)hipGetLastError();
 }
 
+// ------------------------------------- masked argmax + selected log-probability
+// loqa_masked_argmax_lse: out_idx[b] as loqa_masked_argmax (same packed record,
+// same tie rule, token_ids, -1) and out_logprob[b] = x[winner] - logsumexp(x
+// over the ALLOWED tokens of columns 0..V-1), the log-softmax of the selected
+// token after the mask. The winner is the maximum, so with m = max and
+// s = sum exp(x - m) over allowed tokens the result is -log(s); a row whose only
+// allowed token is the winner has s == 1 and gives +0.0f. Nothing allowed, or a
+// winner of -inf, gives -inf (never NaN).
+// Every logit is read once and costs one expf (online softmax per thread, plus
+// one rescaling expf when a vector group raises the thread's maximum); all
+// arithmetic is f32. A workgroup reduces its ARG_CHUNK tokens to one record
+// (packed best, chunk max, chunk sum) in a fixed order; a row of one chunk
+// finishes there, a wider row writes the record to workspace[b][chunk] and a
+// finalize launch merges the row's records in chunk order: no memset, no
+// atomics, and results that are bitwise repeatable.
+struct ArgLse {
+  unsigned long long best;
+  float m, s;
+};
+
+__device__ __forceinline__ void lse_add(float& m, float& s, float x) {
+  if (x == -INFINITY) return;     // weight 0 (and keeps inf - inf out of the sum)
+  const float d = x - m;          // m == -inf: d = +inf, e = 0, s = 0 * 0 + 1
+  const float e = expf(-fabsf(d));
+  if (d > 0.f) {
+    s = s * e + 1.f;
+    m = x;
+  } else {
+    s += e;
+  }
+}
+
+// a vector group: the running maximum moves at most once (one rescaling expf),
+// then the group's expf are independent of each other
+template <int N>
+__device__ __forceinline__ void lse_add_group(float& m, float& s, const float (&f)[N],
+                                              uint32_t bits) {
+  float gm = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < N; ++j)
+    if ((bits >> j) & 1u) gm = fmaxf(gm, f[j]);
+  if (gm == -INFINITY) return;    // nothing allowed in the group, or only -inf
+  if (gm > m) {
+    s *= expf(m - gm);            // m == -inf: s == 0 stays 0
+    m = gm;
+  }
+#pragma unroll
+  for (int j = 0; j < N; ++j)
+    if ((bits >> j) & 1u) s += expf(f[j] - m);   // m finite: -inf gives 0
+}
+
+__device__ __forceinline__ void lse_merge(float& m, float& s, float m2, float s2) {
+  const float mm = fmaxf(m, m2);
+  if (mm == -INFINITY) return;    // both empty: s == s2 == 0
+  s = s * expf(m - mm) + s2 * expf(m2 - mm);
+  m = mm;
+}
+
+__device__ __forceinline__ float lse_logprob(unsigned long long best, float m, float s) {
+  return (best && m != -INFINITY) ? 0.f - logf(s) : -INFINITY;
+}
+
+template <bool BF16, bool SINGLE>
+__global__ __launch_bounds__(ARG_THREADS) void masked_argmax_lse_kernel(
+    const void* __restrict__ logits, long long ld, int V, const uint32_t* __restrict__ mask,
+    const int* __restrict__ mask_rows, int W, ArgLse* __restrict__ part,
+    const int* __restrict__ token_ids, int* __restrict__ out_idx, float* __restrict__ out_logprob) {
+  __shared__ ArgLse sred[ARG_THREADS / 64];
+  const int b = blockIdx.y;
+  const int v_begin = blockIdx.x * ARG_CHUNK;
+  const int v_end = min(V, v_begin + ARG_CHUNK);
+  const uint32_t* m = nullptr;
+  if (mask) m = mask + (size_t)(mask_rows ? mask_rows[b] : b) * W;
+  unsigned long long best = 0;
+  float mx = -INFINITY, sum = 0.f;
+  if (BF16) {
+    const bf16_t* row = reinterpret_cast<const bf16_t*>(logits) + (size_t)b * ld;
+    for (int v0 = v_begin + threadIdx.x * 8; v0 < v_end; v0 += ARG_THREADS * 8) {
+      if (v0 + 8 <= v_end && (ld % 8 == 0)) {
+        float f[8];
+        unpack8(*reinterpret_cast<const uint4*>(row + v0), f);
+        const uint32_t bits = m ? (m[v0 >> 5] >> (v0 & 31)) & 0xffu : 0xffu;
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          if ((bits >> j) & 1u) best = max(best, argpack(f[j], v0 + j));
+        lse_add_group<8>(mx, sum, f, bits);
+      } else {
+        for (int v = v0; v < min(v_end, v0 + 8); ++v)
+          if (!m || ((m[v >> 5] >> (v & 31)) & 1u)) {
+            const float x = bf2f(row[v]);
+            best = max(best, argpack(x, v));
+            lse_add(mx, sum, x);
+          }
+      }
+    }
+  } else {
+    const float* row = reinterpret_cast<const float*>(logits) + (size_t)b * ld;
+    for (int v0 = v_begin + threadIdx.x * 4; v0 < v_end; v0 += ARG_THREADS * 4) {
+      if (v0 + 4 <= v_end && (ld % 4 == 0)) {
+        const float4 f4 = *reinterpret_cast<const float4*>(row + v0);
+        const float f[4] = {f4.x, f4.y, f4.z, f4.w};
+        const uint32_t bits = m ? (m[v0 >> 5] >> (v0 & 31)) & 0xfu : 0xfu;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if ((bits >> j) & 1u) best = max(best, argpack(f[j], v0 + j));
+        lse_add_group<4>(mx, sum, f, bits);
+      } else {
+        for (int v = v0; v < min(v_end, v0 + 4); ++v)
+          if (!m || ((m[v >> 5] >> (v & 31)) & 1u)) {
+            const float x = row[v];
+            best = max(best, argpack(x, v));
+            lse_add(mx, sum, x);
+          }
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long other = __shfl_xor(best, o, 64);
+    best = max(best, other);
+    const float m2 = __shfl_xor(mx, o, 64), s2 = __shfl_xor(sum, o, 64);
+    lse_merge(mx, sum, m2, s2);
+  }
+  if ((threadIdx.x & 63) == 0) sred[threadIdx.x >> 6] = ArgLse{best, mx, sum};
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int i = 1; i < ARG_THREADS / 64; ++i) {
+      best = max(best, sred[i].best);
+      lse_merge(mx, sum, sred[i].m, sred[i].s);
+    }
+    if (SINGLE) {
+      out_idx[b] = argunpack(best, token_ids);
+      out_logprob[b] = lse_logprob(best, mx, sum);
+    } else {
+      part[(size_t)b * gridDim.x + blockIdx.x] = ArgLse{best, mx, sum};
+    }
+  }
+}
+
+// one thread per row: the row's chunk records, merged in chunk order
+__global__ void argmax_lse_finalize_kernel(const ArgLse* __restrict__ part, int B, int chunks,
+                                           const int* __restrict__ token_ids,
+                                           int* __restrict__ out_idx,
+                                           float* __restrict__ out_logprob) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const ArgLse* p = part + (size_t)b * chunks;
+  unsigned long long best = p[0].best;
+  float mx = p[0].m, sum = p[0].s;
+  for (int c = 1; c < chunks; ++c) {
+    best = max(best, p[c].best);
+    lse_merge(mx, sum, p[c].m, p[c].s);
+  }
+  out_idx[b] = argunpack(best, token_ids);
+  out_logprob[b] = lse_logprob(best, mx, sum);
+}
+
+template <bool SINGLE>
+static void launch_masked_argmax_lse(int is_bf16, dim3 grid, hipStream_t s, const void* logits,
+                                     long long ld, int V, const uint32_t* mask,
+                                     const int* mask_rows, int W, ArgLse* part,
+                                     const int* token_ids, int* out_idx, float* out_logprob) {
+  if (is_bf16)
+    hipLaunchKernelGGL((masked_argmax_lse_kernel<true, SINGLE>), grid, dim3(ARG_THREADS), 0, s,
+                       logits, ld, V, mask, mask_rows, W, part, token_ids, out_idx, out_logprob);
+  else
+    hipLaunchKernelGGL((masked_argmax_lse_kernel<false, SINGLE>), grid, dim3(ARG_THREADS), 0, s,
+                       logits, ld, V, mask, mask_rows, W, part, token_ids, out_idx, out_logprob);
+}
+
+// workspace: >= B * ceil(V / ARG_CHUNK) * 16 bytes (device, 8-byte aligned);
+// only touched when V > ARG_CHUNK, and needs no initialisation.
+extern "C" int loqa_masked_argmax_lse(const void* logits, int is_bf16, long long ld, int B, int V,
+                                      const uint32_t* mask, const int* mask_rows, int W,
+                                      int* out_idx, float* out_logprob, void* workspace,
+                                      const int* token_ids, hipStream_t s) {
+  if (B <= 0) return 0;
+  if (V <= 0 || ld < V || (mask && W * 32 < V) || !out_idx || !out_logprob)
+    return (int)hipErrorInvalidValue;
+  if (V <= ARG_CHUNK) {
+    launch_masked_argmax_lse<true>(is_bf16, dim3(1, B), s, logits, ld, V, mask, mask_rows, W,
+                                   nullptr, token_ids, out_idx, out_logprob);
+    return (int)hipGetLastError();
+  }
+  if (!workspace) return (int)hipErrorInvalidValue;
+  const int chunks = (V + ARG_CHUNK - 1) / ARG_CHUNK;
+  launch_masked_argmax_lse<false>(is_bf16, dim3(chunks, B), s, logits, ld, V, mask, mask_rows, W,
+                                  (ArgLse*)workspace, token_ids, out_idx, out_logprob);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(argmax_lse_finalize_kernel, dim3((B + 63) / 64), dim3(64), 0, s,
+                     (const ArgLse*)workspace, B, chunks, token_ids, out_idx, out_logprob);
+  return (int)hipGetLastError();
+}
+
 // ------------------------------------------------- pipelined decode: step I/O
 // A decode step graph exchanges its host data without copy-engine operations
 // between graphs (each H2D / D2H copy on the decode stream cost a copy-engine
@@ -511,6 +706,29 @@ __global__ __launch_bounds__(256) void step_publish_kernel(const int* __restrict
   }
 }
 
+// step_publish_kernel plus the step's token log-probabilities: lp[i] goes to
+// slot (ctr % nres) of a second pinned ring (f32, row stride lp_stride), before
+// the fence and the counter store that order the tokens.
+__global__ __launch_bounds__(256) void step_publish_lp_kernel(
+    const int* __restrict__ out, const float* __restrict__ lp, int n, int* __restrict__ res,
+    int stride, float* __restrict__ res_lp, int lp_stride, int nres, int* __restrict__ ctr,
+    const int* __restrict__ row_slot, int* __restrict__ last_tok) {
+  const int c = ctr[0];
+  int* dst = res + (size_t)(c % nres) * stride;
+  float* dst_lp = res_lp + (size_t)(c % nres) * lp_stride;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const int v = out[i];
+    dst[i] = v;
+    dst_lp[i] = lp[i];
+    last_tok[row_slot[i]] = v;     // padding rows write the trash slot
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __threadfence_system();
+    __hip_atomic_store(ctr, (c + 1) % (2 * nres), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
 // T: token rows at the head of the staged int32 block; src_off: offset of the
 // per-token source-slot array in it (see LLMEngine._decode_graph).
 extern "C" int loqa_step_fetch(void* d32, const void* h32, int n32, int stride32, void* d64,
@@ -531,6 +749,16 @@ extern "C" int loqa_step_publish(const int* out, int n, void* res, int stride, i
   if (n < 0 || n > stride || nres < 1) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(step_publish_kernel, dim3(1), dim3(256), 0, s, out, n, (int*)res, stride, nres, ctr,
                      row_slot, last_tok);
+  return (int)hipGetLastError();
+}
+
+extern "C" int loqa_step_publish_lp(const int* out, const float* lp, int n, void* res, int stride,
+                                    void* res_lp, int lp_stride, int nres, int* ctr,
+                                    const int* row_slot, int* last_tok, hipStream_t s) {
+  if (n < 0 || n > stride || n > lp_stride || nres < 1 || !lp || !res_lp)
+    return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(step_publish_lp_kernel, dim3(1), dim3(256), 0, s, out, lp, n, (int*)res, stride,
+                     (float*)res_lp, lp_stride, nres, ctr, row_slot, last_tok);
   return (int)hipGetLastError();
 }
 

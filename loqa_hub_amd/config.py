@@ -203,6 +203,11 @@ class GPUConfig:
     # per-row scales: half the bytes per decode step; one GPU, gpu backend)
     llm_weights: str = "bf16"
     stt_backend: str = "gpu"          # gpu | http
+    # the transcript's confidence: "heuristic" (the reference's text rules) or
+    # "acoustic" (exp of the mean log-probability of the Whisper tokens; gpu
+    # backend); below stt_confirm_below the hub asks the user to confirm
+    stt_confidence: str = "heuristic"
+    stt_confirm_below: float = 0.6
     tts_backend: str = "gpu"          # gpu | http | none
     use_graphs: bool = True
     seed: int = 0
@@ -315,6 +320,15 @@ class Config:
             if self.gpu.llm_backend != "gpu":
                 raise ConfigError("HUB_LLM_WEIGHTS=fp8 needs HUB_LLM_BACKEND=gpu: "
                                   f"{self.gpu.llm_backend}")
+        if self.gpu.stt_confidence not in ("heuristic", "acoustic"):
+            raise ConfigError("invalid HUB_STT_CONFIDENCE (heuristic | acoustic): "
+                              f"{self.gpu.stt_confidence}")
+        if self.gpu.stt_confidence == "acoustic" and self.gpu.stt_backend != "gpu":
+            raise ConfigError("HUB_STT_CONFIDENCE=acoustic needs HUB_STT_BACKEND=gpu: "
+                              f"{self.gpu.stt_backend}")
+        if not 0.0 <= self.gpu.stt_confirm_below <= 1.0:
+            raise ConfigError("HUB_STT_CONFIRM_BELOW must be in [0, 1]: "
+                              f"{self.gpu.stt_confirm_below}")
 
 
 def parse_relay_groups(s: str) -> dict:
@@ -407,6 +421,8 @@ def load(env=None) -> Config:
             llm_backend=env_str(e, "gpu", "HUB_LLM_BACKEND"),
             llm_weights=env_str(e, "bf16", "HUB_LLM_WEIGHTS").lower(),
             stt_backend=env_str(e, "gpu", "HUB_STT_BACKEND"),
+            stt_confidence=env_str(e, "heuristic", "HUB_STT_CONFIDENCE").lower(),
+            stt_confirm_below=env_float(e, 0.6, "HUB_STT_CONFIRM_BELOW"),
             tts_backend=env_str(e, "gpu", "HUB_TTS_BACKEND"),
             use_graphs=env_bool(e, True, "HUB_USE_GRAPHS"),
             seed=env_int(e, 0, "HUB_SEED"),

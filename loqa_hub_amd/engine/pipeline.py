@@ -22,7 +22,8 @@ from ..llm.commands import (Command, MultiCommand, ParseError, detect_compound_u
                             parse_multi_command_response, parse_response,
                             split_compound_utterance)
 from ..llm.prompts import build_multi_command_prompt, build_prompt
-from ..llm.transcriber import TranscriptionResult, to_transcription_result
+from ..llm.transcriber import (CONFIRMATION_THRESHOLD, TranscriptionResult,
+                               to_transcription_result)
 from ..transport.device_commands import ExecutionContext, NATSCommandExecutor
 from ..utils.faults import faults
 from ..utils.tracing import tracer
@@ -72,8 +73,11 @@ class VoicePipeline:
                  response_audio: bool = False, overlap: bool = True,
                  continuous: bool | None = None, batch_window: float = 0.002,
                  max_batch: int = 8, stt_priority: int = -1,
-                 stt_continuous: bool | None = None):
+                 stt_continuous: bool | None = None,
+                 stt_confirm_below: float = CONFIRMATION_THRESHOLD):
         self.stt, self.llm, self.nats = stt, llm, nats
+        # confirmation threshold of the transcript's confidence (HUB_STT_CONFIRM_BELOW)
+        self.stt_confirm_below = stt_confirm_below
         self.min_response_tokens = min_response_tokens
         self.queue_max_duration = queue_max_duration
         self.rollback = rollback
@@ -128,7 +132,8 @@ class VoicePipeline:
         if fi and fi.active("stt_error"):
             j.stt_failed, j.error = True, "stt: injected fault"
             return
-        j.transcription = to_transcription_result(r.text)
+        # r.avg_logprob: None unless the STT engine records token log-probabilities
+        j.transcription = to_transcription_result(r.text, r.avg_logprob, self.stt_confirm_below)
 
     def build_request(self, j: PipelineJob) -> GenRequest | None:
         if j.stt_failed:

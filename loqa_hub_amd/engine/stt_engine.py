@@ -71,6 +71,12 @@ class STTRequest:
     sumsq: float = 0.0
     rms: float = 0.0
     tokens: list[int] = field(default_factory=list)
+    # STTEngine(token_logprobs=True), free decoding: the log-probability of each
+    # entry of ``tokens`` (the window being decoded; a sampled EOT included) and
+    # the mean over every sampled token of every window (Whisper's avg_logprob).
+    # Teacher-forced requests emit their target, not the sample: empty / None.
+    logprobs: list[float] = field(default_factory=list)
+    avg_logprob: float | None = None
     seq_id: int = -1
     t_done: float = 0.0
     t_enc0: float = 0.0               # encoder start / end, decoder start (perf_counter)
@@ -90,6 +96,8 @@ class STTRequest:
     win_texts: list = field(default_factory=list)
     prev_tokens: list = field(default_factory=list)
     prompt_steps: int = 1
+    lp_sum: float = 0.0               # finished windows' log-probability sum / count
+    lp_n: int = 0
 
 
 class STTEngine:
@@ -100,8 +108,12 @@ class STTEngine:
     def __init__(self, cfg: WhisperConfig, device, *, seed: int = 0, max_batch: int = 64,
                  block_size: int = 16, use_graphs: bool = True, fast_decode: bool = True,
                  fused: bool = True, weights: WhisperWeights | None = None,
-                 contended_tuning: bool = False, tokenizer=None, language: str = "en"):
+                 contended_tuning: bool = False, tokenizer=None, language: str = "en",
+                 token_logprobs: bool = False):
         self.cfg = cfg
+        # every step also returns the log-softmax (after the suppress mask) of
+        # the token it samples (ops.masked_argmax_logprob); off: ops.masked_argmax
+        self.token_logprobs = token_logprobs
         self.device = torch.device(device)
         if self.device.type == "cuda" and self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
@@ -151,6 +163,8 @@ class STTEngine:
         self._next = 1
         self.stats = {"utterances": 0, "decode_steps": 0, "host_pre_s": 0.0, "gpu_wait_s": 0.0,
                       "encode_s": 0.0}
+        if token_logprobs:
+            self.stats.update(logprob_tokens=0, logprob_sum=0.0)
         self.max_batch = max_batch
         self.fast_decode = fast_decode
         # fused-epilogue decoder GEMMs (8 launches per layer) for Mpad <= 64
@@ -199,6 +213,9 @@ class STTEngine:
             self._stage32 = torch.zeros(2, self._n32_max, dtype=torch.int32).pin_memory()
             self._stage64 = torch.zeros(2, self._n64_max, dtype=torch.int64).pin_memory()
             self._res_ring = torch.zeros(self.RES_SLOTS, 256, dtype=torch.int32).pin_memory()
+            # the steps' token log-probabilities, same slots (loqa_step_publish_lp)
+            self._res_lp_ring = torch.zeros(self.RES_SLOTS, 256, dtype=torch.float32).pin_memory() \
+                if token_logprobs else None
             self._step_ctr = torch.zeros(1, dtype=torch.int32, device=self.device)
             self._step_no = 0
             self.last_tok = torch.zeros(max_batch + 1, dtype=torch.int32, device=self.device)
@@ -380,12 +397,20 @@ class STTEngine:
             return self.self_splits
         return max(1, min(self.self_splits, (ctx + self.SPLIT_KEYS - 1) // self.SPLIT_KEYS))
 
-    def _argmax(self, logits: torch.Tensor) -> torch.Tensor:
+    def _argmax(self, logits: torch.Tensor):
+        """Sampled tokens; with ``token_logprobs`` (tokens, their log-probabilities)."""
+        fn = ops.masked_argmax_logprob if self.token_logprobs else ops.masked_argmax
         if self._sup is None:
-            return ops.masked_argmax(logits)
-        return ops.masked_argmax(logits, self._sup, self._sup_rows[: logits.shape[0]])
+            return fn(logits)
+        return fn(logits, self._sup, self._sup_rows[: logits.shape[0]])
 
-    def _fast_forward(self, dev: dict, max_q: int, B_pad: int, ctx: int | None = None) -> torch.Tensor:
+    def _host(self, res, B: int | None = None):
+        """A step's device result (``_argmax``) as numpy, cut to B rows."""
+        if self.token_logprobs:
+            return res[0][:B].cpu().numpy(), res[1][:B].cpu().numpy()
+        return res[:B].cpu().numpy()
+
+    def _fast_forward(self, dev: dict, max_q: int, B_pad: int, ctx: int | None = None):
         ns = self._self_splits(ctx)
         if self.fused and dev["tokens"].numel() <= 64:
             logits = decode_step_fused(self.model, dev["tokens"], dev["positions"], dev["slots"],
@@ -448,10 +473,17 @@ class STTEngine:
                 self._stage64.data_ptr(), L, self._n64_max, lib.ptr(self._step_ctr), T_pad, src_off,
                 lib.ptr(self.last_tok), st), "step_fetch")
             out = self._fast_forward(dev, max_q, B_pad, ctx)
-            lib.check(k.loqa_step_publish(
-                lib.ptr(out), B_pad, self._res_ring.data_ptr(), self._res_ring.shape[1],
-                self.RES_SLOTS, lib.ptr(self._step_ctr), lib.ptr(dev["row_slot"]),
-                lib.ptr(self.last_tok), st), "step_publish")
+            if self.token_logprobs:
+                lib.check(k.loqa_step_publish_lp(
+                    lib.ptr(out[0]), lib.ptr(out[1]), B_pad, self._res_ring.data_ptr(),
+                    self._res_ring.shape[1], self._res_lp_ring.data_ptr(),
+                    self._res_lp_ring.shape[1], self.RES_SLOTS, lib.ptr(self._step_ctr),
+                    lib.ptr(dev["row_slot"]), lib.ptr(self.last_tok), st), "step_publish_lp")
+            else:
+                lib.check(k.loqa_step_publish(
+                    lib.ptr(out), B_pad, self._res_ring.data_ptr(), self._res_ring.shape[1],
+                    self.RES_SLOTS, lib.ptr(self._step_ctr), lib.ptr(dev["row_slot"]),
+                    lib.ptr(self.last_tok), st), "step_publish")
         g = {"graph": graph, "dev": dev, "out": out, "shapes": shapes, "n32": n32, "L": L}
         self._graphs[key] = g
         return g
@@ -543,8 +575,9 @@ class STTEngine:
         self._graphs_frozen = True
         return n
 
-    def _step(self, live: list[STTRequest]) -> np.ndarray:
-        """One decoder step for every live request (its ``feed`` tokens)."""
+    def _step(self, live: list[STTRequest]):
+        """One decoder step for every live request (its ``feed`` tokens): the
+        sampled tokens, with ``token_logprobs`` (tokens, log-probabilities)."""
         B = len(live)
         T = sum(len(r.feed) for r in live)
         if self.fast_decode:
@@ -563,14 +596,16 @@ class STTEngine:
                 rslot = self._replay(g)
                 torch.cuda.current_stream(self.device).synchronize()
                 out = self._res_ring[rslot, :B].numpy().copy()
+                if self.token_logprobs:
+                    out = out, self._res_lp_ring[rslot, :B].numpy().copy()
                 self.stats["host_pre_s"] += t1 - t0
                 self.stats["gpu_wait_s"] += time.perf_counter() - t1
                 return out
             max_q, host = self._host_meta(live, B_pad, T_pad)
-            return self._fast_forward(self._dev(host), max_q, B_pad)[:B].cpu().numpy()
+            return self._host(self._fast_forward(self._dev(host), max_q, B_pad), B)
         return self._eager_step(live)
 
-    def _eager_step(self, live: list[STTRequest]) -> np.ndarray:
+    def _eager_step(self, live: list[STTRequest]):
         """Reference decode path (hipBLASLt GEMMs, eager launches)."""
         T_enc = self.cfg.n_audio_ctx
         toks, pos, slots, cu, ctx, lidx = [], [], [], [0], [], []
@@ -597,7 +632,7 @@ class STTEngine:
             dev(toks, torch.int32), dev(pos, torch.int32), dev(slots, torch.int32),
             dev(cu, torch.int32), dev(ctx, torch.int32), dev(bt, torch.int32), max_q, max_ctx,
             self.kv.k, self.kv.v, self.xkv, enc_starts, enc_lens, dev(lidx, torch.int64), self.ws)
-        return self._argmax(logits).cpu().numpy()
+        return self._host(self._argmax(logits))
 
     # ----------------------------------------------------------- admission
     def _admit(self, reqs: list[STTRequest], slots: list[int],
@@ -654,6 +689,7 @@ class STTEngine:
             r.t_dec0 = now
             r.t_done = 0.0
             r.win_texts, r.prev_tokens = [], []
+            r.lp_sum, r.lp_n, r.avg_logprob = 0.0, 0, None
             if not r.slots:
                 r.slots = [r.slot]
             self._begin_window(r, 0)
@@ -682,6 +718,7 @@ class STTEngine:
         if w > 0 and self.sop is not None and r.prev_tokens and PREV_TOKENS > 0:
             prompt = [self.sop] + r.prev_tokens[-PREV_TOKENS:]
         r.tokens, r.step, r.feed = [], 0, prompt + list(self.sot)
+        r.logprobs = []
         r.prompt_steps = -(-len(r.feed) // len(self.sot))
         r.target = None
         text = self._window_text(r, w)
@@ -703,6 +740,9 @@ class STTEngine:
                 r.feed = r.feed[:n]
         live = step
         nxt = self._step(live)
+        lps = None
+        if self.token_logprobs:
+            nxt, lps = nxt
         self.stats["decode_steps"] += 1
         done = []
         for j, r in enumerate(live):
@@ -711,6 +751,8 @@ class STTEngine:
                 continue
             t = int(r.target[r.step]) if r.target is not None else int(nxt[j])
             r.tokens.append(t)
+            if lps is not None and r.target is None:
+                r.logprobs.append(float(lps[j]))
             r.step += 1
             if t == self.eot or len(r.tokens) >= r.max_new_tokens or \
                     (r.target is not None and r.step >= len(r.target)):
@@ -728,12 +770,21 @@ class STTEngine:
         r.win_texts.append(self.tok.decode(toks).strip())
         r.prev_tokens = (r.prev_tokens + toks)[-max(PREV_TOKENS, 1):]
         self.kv.pool.free_seq(r.seq_id)
+        if r.logprobs:
+            # fp64 sum of the window's f32 values; -inf (nothing allowed) stays -inf
+            r.lp_sum += float(np.sum(np.asarray(r.logprobs, np.float64)))
+            r.lp_n += len(r.logprobs)
         if r.win + 1 < r.windows:
             self.stats["long_form_windows"] = self.stats.get("long_form_windows", 0) + 1
             self._begin_window(r, r.win + 1)
             return None
         r.t_done = time.perf_counter()
         r.text = " ".join(t for t in r.win_texts if t)
+        if r.lp_n:
+            r.avg_logprob = r.lp_sum / r.lp_n
+            if np.isfinite(r.lp_sum):       # a step with nothing allowed is -inf
+                self.stats["logprob_tokens"] += r.lp_n
+                self.stats["logprob_sum"] += r.lp_sum
         self.stats["utterances"] += 1
         return r
 

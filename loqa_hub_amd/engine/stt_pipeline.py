@@ -31,10 +31,11 @@ DEV = -1   # feed placeholder: the token this request sampled in its previous st
 
 
 class _Step:
-    __slots__ = ("rows", "B", "out", "event", "entries")
+    __slots__ = ("rows", "B", "out", "event", "entries", "lp")
 
-    def __init__(self, rows, B, out, event, entries):
+    def __init__(self, rows, B, out, event, entries, lp=None):
         self.rows, self.B, self.out, self.event, self.entries = rows, B, out, event, entries
+        self.lp = lp        # the step's token log-probabilities (engine token_logprobs)
 
 
 class STTPipeline:
@@ -166,7 +167,8 @@ class STTPipeline:
             r.pl_fl += 1
             if sp:
                 self.stats["pl_spec"] += 1
-        self.inflight.append(_Step(rows, B, eng._res_ring[rslot], ev, entries))
+        lp = eng._res_lp_ring[rslot] if eng.token_logprobs else None
+        self.inflight.append(_Step(rows, B, eng._res_ring[rslot], ev, entries, lp))
         self.stats["pl_steps"] += 1
         eng.stats["decode_steps"] += 1
         return True
@@ -180,6 +182,10 @@ class STTPipeline:
         for r, f in zip(rows, feeds):
             r.feed = f
         out = self.eng._step(rows)
+        lp = None
+        if self.eng.token_logprobs:
+            out, lp = out
+            lp = torch.from_numpy(np.asarray(lp, np.float32))
         for r, f in zip(rows, saved):
             r.feed = f
         # the eager step does not run the graphs' publish node: keep last_tok
@@ -193,7 +199,7 @@ class STTPipeline:
             r.pl_launched += 1
             r.pl_fl += 1
         self.inflight.append(_Step(rows, len(rows), torch.from_numpy(np.asarray(out, np.int32)),
-                                   None, entries))
+                                   None, entries, lp))
         self.eng.stats["decode_steps"] += 1
         return True
 
@@ -204,6 +210,7 @@ class STTPipeline:
         if st.event is not None:
             st.event.synchronize()
         nxt = st.out[: st.B].numpy().copy()
+        lps = st.lp[: st.B].numpy().copy() if st.lp is not None else None
         eng.stats["gpu_wait_s"] += time.perf_counter() - t0
         done = []
         for b, (r, (k, sp)) in enumerate(zip(st.rows, st.entries)):
@@ -217,8 +224,10 @@ class STTPipeline:
                 continue
             t = int(r.target[k]) if r.target is not None else int(nxt[b])
             r.tokens.append(t)
+            if lps is not None and r.target is None:
+                r.logprobs.append(float(lps[b]))
             r.step += 1
-            end = (t == eng.eot or len(r.tokens) >= r.max_new_tokens
+            end =(t == eng.eot or len(r.tokens) >= r.max_new_tokens
                    or (r.target is not None and r.step >= len(r.target)))
             if end:
                 r.pl_end = True

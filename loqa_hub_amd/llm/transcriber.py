@@ -10,6 +10,7 @@ confidence < 0.6 or only the wake word was spoken) and ``:461-513``
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from typing import Protocol
 
@@ -27,6 +28,7 @@ class TranscriptionResult:
     wake_word_detected: bool = False
     wake_word_variant: str = ""
     needs_confirmation: bool = False
+    avg_logprob: float | None = None   # mean Whisper token log-probability (acoustic confidence)
 
 
 @dataclass
@@ -89,7 +91,18 @@ def post_process_transcription(raw: str) -> PostProcessingResult:
     return res
 
 
-def to_transcription_result(raw: str) -> TranscriptionResult:
+def to_transcription_result(raw: str, avg_logprob: float | None = None,
+                            confirm_below: float = CONFIRMATION_THRESHOLD) -> TranscriptionResult:
+    """``avg_logprob`` (the on-device Whisper decode's mean token
+    log-probability): the confidence is the geometric-mean token probability
+    ``min(1, exp(avg_logprob))`` instead of the text heuristic, and a
+    confirmation is needed below ``confirm_below``. None: the reference's
+    heuristic and threshold. The wake-word-only rule holds either way."""
     p = post_process_transcription(raw)
-    return TranscriptionResult(p.cleaned_text, p.confidence_estimate, p.wake_word_detected,
-                               p.wake_word_variant, p.needs_confirmation)
+    if avg_logprob is None:
+        return TranscriptionResult(p.cleaned_text, p.confidence_estimate, p.wake_word_detected,
+                                   p.wake_word_variant, p.needs_confirmation)
+    conf = min(1.0, math.exp(avg_logprob))
+    confirm = conf < confirm_below or (p.wake_word_detected and p.cleaned_text == "")
+    return TranscriptionResult(p.cleaned_text, conf, p.wake_word_detected, p.wake_word_variant,
+                               confirm, avg_logprob)

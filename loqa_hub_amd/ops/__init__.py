@@ -295,6 +295,49 @@ def masked_argmax(logits: torch.Tensor, mask: torch.Tensor | None = None,
     return out
 
 
+ARG_CHUNK = 8192    # tokens per workgroup of the argmax kernels (elementwise.hip)
+
+
+def masked_argmax_logprob(logits: torch.Tensor, mask: torch.Tensor | None = None,
+                          mask_rows: torch.Tensor | None = None,
+                          token_ids: torch.Tensor | None = None
+                          ) -> tuple[torch.Tensor, torch.Tensor]:
+    """``masked_argmax`` and the log-probability of the token it selects:
+    ``x[winner] - logsumexp(x over the allowed tokens)``, the log-softmax after
+    the mask, in fp32. Returns (int32 [B], float32 [B]); a row with nothing
+    allowed gives (-1, -inf), a row whose only allowed token wins gives 0.0.
+    One launch for V <= 8192, else per-chunk partials and a fixed-order merge
+    (no memset, no atomics: bitwise repeatable)."""
+    if token_ids is not None:
+        assert token_ids.dtype == torch.int32 and token_ids.is_contiguous()
+        assert token_ids.numel() >= logits.shape[-1] and token_ids.device == logits.device
+    if not _gpu(logits):
+        return ref.masked_argmax_logprob(logits, mask, mask_rows, token_ids)
+    assert logits.dim() == 2 and logits.stride(-1) == 1
+    B, V = logits.shape
+    W = 0
+    if mask is not None:
+        assert mask.dtype == torch.int32 and mask.is_contiguous()
+        W = mask.shape[-1]
+        assert W * 32 >= V
+        if mask_rows is not None:
+            assert mask_rows.dtype == torch.int32 and mask_rows.numel() == B
+        else:
+            assert mask.shape[0] >= B
+    is_bf16 = logits.dtype == torch.bfloat16
+    assert is_bf16 or logits.dtype == torch.float32
+    out = torch.empty(B, dtype=torch.int32, device=logits.device)
+    lp = torch.empty(B, dtype=torch.float32, device=logits.device)
+    chunks = (V + ARG_CHUNK - 1) // ARG_CHUNK
+    # 16-byte chunk records [B, chunks] (written before they are read)
+    ws = torch.empty(B * chunks * 2, dtype=torch.int64, device=logits.device) if chunks > 1 else None
+    check(kernels().loqa_masked_argmax_lse(ptr(logits), int(is_bf16), logits.stride(0), B, V,
+                                           ptr(mask), ptr(mask_rows), W, ptr(out), ptr(lp),
+                                           ptr(ws), ptr(token_ids), stream_ptr(logits)),
+          "masked_argmax_lse")
+    return out, lp
+
+
 # -------------------------------------------------------------------- audio
 def pcm16_to_f32_sumsq(pcm: torch.Tensor, offsets: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     """pcm: int16 [N] (concatenated segments), offsets: int64 [S+1].

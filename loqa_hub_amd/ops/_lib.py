@@ -148,6 +148,12 @@ _KERNEL_SIGS = {
     "loqa_init_uniform4": [c_void_p, c_ll, c_int, c_ll, c_ll, c_ll, ctypes.c_uint, c_float, c_void_p],
     "loqa_step_publish": [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                           c_void_p],
+    "loqa_masked_argmax_lse": [c_void_p, c_int, c_ll, c_int, c_int, c_void_p, c_void_p, c_int,
+                               # (..., out_idx, out_logprob, workspace, token_ids, stream)
+                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    # (out, logprobs, n, res, stride, res_lp, lp_stride, nres, ctr, row_slot, last_tok, stream)
+    "loqa_step_publish_lp": [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
+                             c_void_p, c_void_p, c_void_p, c_void_p],
 }
 
 # (argtypes, restype) of the custom all-reduce entry points (in the kernels library)

@@ -160,6 +160,23 @@ def masked_argmax(logits, mask=None, mask_rows=None, token_ids=None):
     return r
 
 
+def masked_argmax_logprob(logits, mask=None, mask_rows=None, token_ids=None):
+    """``masked_argmax`` plus the selected token's log-softmax over the allowed
+    tokens (masked fill, then ``log_softmax`` in fp32). Nothing allowed, or a
+    winner of -inf: -inf (never NaN)."""
+    idx = masked_argmax(logits, mask, mask_rows, token_ids)
+    x = logits.float()
+    B, V = x.shape
+    if mask is not None:
+        m = mask if mask_rows is None else mask[mask_rows.long()]
+        x = x.masked_fill(~unpack_mask(m, V), float("-inf"))
+    col = x.argmax(dim=-1, keepdim=True)
+    lp = torch.log_softmax(x, dim=-1).gather(1, col)[:, 0]
+    top = x.gather(1, col)[:, 0]
+    lp = torch.where(torch.isinf(top) & (top < 0), torch.full_like(lp, float("-inf")), lp)
+    return idx, lp
+
+
 def unpack_mask(m: torch.Tensor, V: int) -> torch.Tensor:
     """int32 words [..., W] -> bool [..., V]"""
     shifts = torch.arange(32, device=m.device, dtype=torch.int32)

@@ -30,7 +30,7 @@ import numpy as np
 
 from ..llm.command_queue import CommandQueue
 from ..llm.commands import MultiCommand
-from ..llm.transcriber import TranscriptionResult
+from ..llm.transcriber import CONFIRMATION_THRESHOLD, TranscriptionResult
 from .audio_service import (MSG_NO_COMMANDS, MSG_NO_SPEECH, MSG_PARSE_FAILED, MSG_STT_FAILED,
                             UtteranceResult)
 from ..utils.faults import faults
@@ -88,7 +88,7 @@ class GPUVoiceProcessor:
         self._speaking: dict[str, object] = {}   # relay id -> its reply still being spoken
         pipeline.batch_window, pipeline.max_batch = batch_window, max_batch
         self.stats = {"utterances": 0, "errors": 0, "bridge_sessions": 0, "bridge_ack": 0,
-                      "bridge_fallback": 0, "interrupted": 0,
+                      "bridge_fallback": 0, "interrupted": 0, "stt_low_confidence": 0,
                       "progressive": 0, "first_audio_ms_sum": 0.0, "first_audio_n": 0}
         # a list that collects every finished PipelineJob (phase timestamps for
         # a benchmark's per-phase breakdown); None: not collected
@@ -185,6 +185,17 @@ class GPUVoiceProcessor:
         ok = None if j.queue is None else j.queue.success
         r = _result_from(text, j.multi, ok, j.transcription)
         r.metrics = {"t": dict(j.t)}
+        tr = j.transcription
+        if tr is not None:
+            # the confidence the confirmation decision was taken on (avg_logprob:
+            # None with the heuristic, HUB_STT_CONFIDENCE)
+            r.metrics["stt"] = {"confidence": tr.confidence_estimate,
+                                "avg_logprob": tr.avg_logprob}
+            below = CONFIRMATION_THRESHOLD      # the heuristic keeps the reference's threshold
+            if tr.avg_logprob is not None:
+                below = getattr(self.pipeline, "stt_confirm_below", below)
+            if tr.confidence_estimate < below:
+                self.stats["stt_low_confidence"] += 1
         if self.bridge is not None and r.success and j.multi is not None and j.multi.commands:
             await self._bridge(r, j, ack=speech is None)
         if speech is not None:
