@@ -18,8 +18,11 @@
 //
 // This header holds the kernels and their launch templates; gemm_skinny.hip
 // instantiates the bf16 weight stream and owns the entry points,
-// gemm_skinny_fp8.hip instantiates the fp8 (e4m3) weight stream - two
-// translation units, so the two sets compile side by side.
+// gemm_skinny_fp8.hip instantiates the fp8 (e4m3) weight stream and
+// gemm_skinny_mxfp4.hip the MXFP4 (e2m1 + e8m0 block scale) one - three
+// translation units, so the sets compile side by side. The format is the FMT
+// parameter of the shared pieces: the weight fragment (WFrag), its load
+// (load_w), the MFMA step that dequantises it (mma_step) and the launcher.
 #pragma once
 #include <type_traits>
 
@@ -47,6 +50,27 @@ __device__ __forceinline__ bf16x8 ldw(const void* p) {
 // registers (half the in-flight weight VGPRs); it is converted to bf16 - exactly,
 // every e4m3 value is a bf16 value - when its group is consumed.
 typedef unsigned char fp8_t;
+
+// The weight stream's format, the FMT parameter of everything below
+enum { WF_BF16 = 0, WF_FP8 = 1, WF_MXFP4 = 2 };
+
+// MXFP4 weight stream (OCP e2m1 elements, one e8m0 scale per 32 k values of a
+// row, gemm_skinny_mxfp4.hip): Wp4[N/16][K/128][64 lanes][16 B]; lane l holds
+// row (l&15), bytes 4j..4j+3 = the 8 k values at offset 8*(l>>4) of k-step
+// 4g+j, ascending, two per byte, the even k in the low nibble. One 16-byte
+// lane load is the A fragments of FOUR k-steps and stays raw in the prefetch
+// registers (a quarter of the in-flight weight VGPRs); an 8-byte load is two
+// k-steps (the layouts whose prefetch group is 2 k-steps).
+// Scales: Ws[N/16][K/128][16 rows][4 B], byte j = the e8m0 scale of k-step
+// 4g+j: a lane reads one dword per 16-byte weight load, the four lanes of a
+// row the same one. A block of 32 is one k-step, so a k-step's A fragment is
+// dequantised in registers as e2m1 * 2^(byte - 127), exactly (every such
+// product the quantiser emits is a normal bf16), and the accumulator needs no
+// scale afterwards.
+struct Mx4Ptr {
+  const unsigned char* w;   // this lane's 16 bytes of the tile's first 4 k-steps
+  const unsigned char* s;   // this lane's row's 4 scale bytes of them
+};
 template <typename W> constexpr int kFp8 = sizeof(W) == 1;
 
 // 8 e4m3 bytes -> the 8 bf16 of one MFMA A fragment: gfx950's packed
@@ -70,9 +94,9 @@ __device__ __forceinline__ bf16x8 cvt_fp8x8(unsigned lo, unsigned hi) {
 
 // A fragment of k-step u of a prefetch slot: bf16 - the register itself; fp8 -
 // half of raw load u / 2
-template <int FP8>
+template <int FMT>
 __device__ __forceinline__ bf16x8 wfrag(const bf16x8& raw, int u) {
-  if constexpr (FP8) {
+  if constexpr (FMT == WF_FP8) {
     const u32x4 v = *reinterpret_cast<const u32x4*>(&raw);
     return (u & 1) ? cvt_fp8x8(v.z, v.w) : cvt_fp8x8(v.x, v.y);
   } else {
@@ -94,62 +118,121 @@ __device__ __forceinline__ void lds_barrier() {
   asm volatile("" ::: "memory");
 }
 
+// 8 e2m1 nibbles (one dword: 8 ascending k values, the even k in the low
+// nibble) times 2^(e8m0 - 127) -> the 8 bf16 of one MFMA A fragment: gfx950's
+// packed fp4 -> bf16 convert, two values per instruction, byte by byte. The
+// scale operand is the f32 whose exponent field is the e8m0 byte. Checked on
+// the hardware through the real kernel (tests/test_mxfp4_weights.py, the
+// convert probe): byte_sel b converts byte b of the source, its low nibble to
+// the low bf16 and its high nibble to the high one; the result is
+// e2m1 * 2^(byte - 127) for every scale byte 2..252 (the quantiser's range;
+// 0 would be the f32 0.0, not 2^-127, and 255 a NaN - neither is emitted);
+// all 16 codes at all 32 nibble positions of a lane load equal the table
+// dequantisation bit for bit.
+__device__ __forceinline__ bf16x8 cvt_mxfp4x8(unsigned q, unsigned e8m0) {
+  typedef __bf16 bf16x2_ __attribute__((ext_vector_type(2)));
+  const float sc = __builtin_bit_cast(float, e8m0 << 23);
+  u32x4 r;
+  r.x = __builtin_bit_cast(unsigned, (bf16x2_)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, sc, 0));
+  r.y = __builtin_bit_cast(unsigned, (bf16x2_)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, sc, 1));
+  r.z = __builtin_bit_cast(unsigned, (bf16x2_)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, sc, 2));
+  r.w = __builtin_bit_cast(unsigned, (bf16x2_)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, sc, 3));
+  return *reinterpret_cast<bf16x8*>(&r);
+}
+
 // One prefetch group of weights: U k-steps of RT row tiles.
 // NW: 16-byte weight loads per row tile and group (fp8: one per two k-steps)
-template <int RT, int U, int FP8 = 0>
+template <int RT, int U, int FMT = 0>
 struct WFrag {
-  static constexpr int NW = FP8 ? (U + 1) / 2 : U;
+  static constexpr int NW = FMT ? (U + 1) / 2 : U;
   bf16x8 a[NW][RT];
 };
 
+// MXFP4: one raw dword (8 nibbles) per k-step and row tile, and the scale
+// bytes of the group's k-steps in one register (U = 4: a dword, U = 2: the
+// two bytes of its k-steps)
+template <int RT, int U>
+struct WFrag<RT, U, WF_MXFP4> {
+  unsigned q[U][RT];
+  unsigned s[RT];
+};
+
 // ... and the group's activation fragments (the register form; XL reads them from LDS)
-template <int RT, int MT, int U, int FP8 = 0>
-struct Frag : WFrag<RT, U, FP8> {
+template <int RT, int MT, int U, int FMT = 0>
+struct Frag : WFrag<RT, U, FMT> {
   bf16x8 b[U][MT];
 };
 
 // wp: this lane's 16 bytes of the tile's first k-step; in elements of W a
 // k-step is 512 apart in both formats (fp8: ks even)
-template <int RT, int U, int FP8, typename W>
-__device__ __forceinline__ void load_w(WFrag<RT, U, FP8>& f, const W* wp, size_t tile_stride, int ks) {
-  static_assert(FP8 == kFp8<W>, "fragment / weight format mismatch");
+template <int RT, int U, int FMT, typename W>
+__device__ __forceinline__ void load_w(WFrag<RT, U, FMT>& f, const W* wp, size_t tile_stride, int ks) {
+  static_assert(FMT == kFp8<W>, "fragment / weight format mismatch");
 #pragma unroll
-  for (int u = 0; u < WFrag<RT, U, FP8>::NW; ++u)
+  for (int u = 0; u < WFrag<RT, U, FMT>::NW; ++u)
 #pragma unroll
     for (int i = 0; i < RT; ++i)
-      f.a[u][i] = ldw(wp + (size_t)i * tile_stride + (size_t)(ks + u * (FP8 ? 2 : 1)) * 512);
+      f.a[u][i] = ldw(wp + (size_t)i * tile_stride + (size_t)(ks + u * (FMT ? 2 : 1)) * 512);
 }
 
-template <int RT, int MT, int U, int FP8>
-__device__ __forceinline__ void load_frag_x(Frag<RT, MT, U, FP8>& f, const bf16_t* xp, long long ldx_, int ks) {
+// MXFP4: tile_stride in bytes of the nibble stream (16 rows x K / 2); the
+// scale stream's is a sixteenth of it. A group of 4 k-steps (ks % 4 == 0) is
+// one 16-byte load and one scale dword; a group of 2 (ks even) the 8 bytes and
+// the 2 scale bytes of its k-steps inside them, so k-steps stay ascending.
+template <int RT, int U, int FMT>
+__device__ __forceinline__ void load_w(WFrag<RT, U, FMT>& f, const Mx4Ptr wp, size_t tile_stride, int ks) {
+  static_assert(FMT == WF_MXFP4 && (U == 4 || U == 2), "MXFP4: prefetch groups of 4 or 2 k-steps");
+  const size_t blk = (size_t)(ks >> 2), sub = (size_t)(ks & 3);
+#pragma unroll
+  for (int i = 0; i < RT; ++i) {
+    const unsigned char* pw = wp.w + (size_t)i * tile_stride + blk * 1024 + sub * 4;
+    const unsigned char* ps = wp.s + (size_t)i * (tile_stride >> 4) + blk * 64 + sub;
+    if constexpr (U == 4) {
+      const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(pw));
+      f.q[0][i] = v.x, f.q[1][i] = v.y, f.q[2][i] = v.z, f.q[3][i] = v.w;
+      f.s[i] = __builtin_nontemporal_load(reinterpret_cast<const unsigned*>(ps));
+    } else {
+      typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+      const u32x2 v = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(pw));
+      f.q[0][i] = v.x, f.q[1][i] = v.y;
+      f.s[i] = __builtin_nontemporal_load(reinterpret_cast<const unsigned short*>(ps));
+    }
+  }
+}
+
+template <int RT, int MT, int U, int FMT>
+__device__ __forceinline__ void load_frag_x(Frag<RT, MT, U, FMT>& f, const bf16_t* xp, long long ldx_, int ks) {
 #pragma unroll
   for (int u = 0; u < U; ++u)
 #pragma unroll
     for (int j = 0; j < MT; ++j) f.b[u][j] = ldx(xp + (size_t)j * 16 * ldx_ + (size_t)(ks + u) * 32);
 }
 
-template <int RT, int MT, int U, int FP8, typename W>
-__device__ __forceinline__ void load_frag(Frag<RT, MT, U, FP8>& f, const W* wp, size_t tile_stride,
+template <int RT, int MT, int U, int FMT, typename WP>
+__device__ __forceinline__ void load_frag(Frag<RT, MT, U, FMT>& f, const WP wp, size_t tile_stride,
                                           const bf16_t* xp, long long ldx_, int ks) {
-  load_w<RT, U, FP8>(f, wp, tile_stride, ks);
+  load_w<RT, U, FMT>(f, wp, tile_stride, ks);
   load_frag_x(f, xp, ldx_, ks);
 }
 
-// k-step u of a group against its MT activation fragments. fp8: this
+// k-step u of a group against its MT activation fragments. fp8 / MXFP4: this
 // k-step's A fragments are dequantised once, here (k-steps stay in ascending
 // order). bf16 reads the prefetch registers in place: going through the same
 // local copy is not free - it took skinny_fused_kernel<1, 2, 4, 4, act> from
 // occupancy 4 to 3 (docs/PERF.md, "Decode GEMM header")
-template <int RT, int MT, int U, int FP8>
-__device__ __forceinline__ void mma_step(const WFrag<RT, U, FP8>& f, int u, const bf16x8 (&b)[MT],
+template <int RT, int MT, int U, int FMT>
+__device__ __forceinline__ void mma_step(const WFrag<RT, U, FMT>& f, int u, const bf16x8 (&b)[MT],
                                          float4v (&acc)[RT][MT]) {
-  bf16x8 deq[FP8 ? RT : 1];
-  if constexpr (FP8) {
+  bf16x8 deq[FMT ? RT : 1];
+  if constexpr (FMT == WF_FP8) {
 #pragma unroll
     for (int i = 0; i < RT; ++i) deq[i] = wfrag<1>(f.a[u / 2][i], u);
+  } else if constexpr (FMT == WF_MXFP4) {
+#pragma unroll
+    for (int i = 0; i < RT; ++i) deq[i] = cvt_mxfp4x8(f.q[u][i], (f.s[i] >> (8 * u)) & 0xffu);
   }
   auto a = [&](int i) -> const bf16x8& {
-    if constexpr (FP8) return deq[i];
+    if constexpr (FMT) return deq[i];
     else return f.a[u][i];
   };
 #pragma unroll
@@ -158,10 +241,10 @@ __device__ __forceinline__ void mma_step(const WFrag<RT, U, FP8>& f, int u, cons
     for (int i = 0; i < RT; ++i) acc[i][j] = mfma16(a(i), b[j], acc[i][j]);
 }
 
-template <int RT, int MT, int U, int FP8>
-__device__ __forceinline__ void mma_frag(const Frag<RT, MT, U, FP8>& f, float4v (&acc)[RT][MT]) {
+template <int RT, int MT, int U, int FMT>
+__device__ __forceinline__ void mma_frag(const Frag<RT, MT, U, FMT>& f, float4v (&acc)[RT][MT]) {
 #pragma unroll
-  for (int u = 0; u < U; ++u) mma_step<RT, MT, U, FP8>(f, u, f.b[u], acc);
+  for (int u = 0; u < U; ++u) mma_step<RT, MT, U, FMT>(f, u, f.b[u], acc);
 }
 
 // Ping-pong stream over ng groups of U k-steps from k-step ks0; f0 already
@@ -174,9 +257,9 @@ __device__ __forceinline__ void mma_frag(const Frag<RT, MT, U, FP8>& f, float4v 
 // (Groups are visited in ascending order. A k-start rotation per workgroup
 // measured 5-10 % SLOWER on every shape: the in-step x reuse across
 // neighbouring workgroups in L2 matters more.)
-template <int RT, int MT, int U, int FP8, typename W>
-__device__ __forceinline__ void stream_k(Frag<RT, MT, U, FP8>& f0, Frag<RT, MT, U, FP8>& f1,
-                                         float4v (&acc)[RT][MT], const W* wp,
+template <int RT, int MT, int U, int FMT, typename WP>
+__device__ __forceinline__ void stream_k(Frag<RT, MT, U, FMT>& f0, Frag<RT, MT, U, FMT>& f1,
+                                         float4v (&acc)[RT][MT], const WP wp,
                                          size_t tile_stride, const bf16_t* xp, long long ldx_,
                                          int ks0, int ng) {
   auto ks = [&](int g) { return ks0 + g * U; };
@@ -211,7 +294,7 @@ __device__ __forceinline__ void skinny_gemm_body(float4v (&red)[3][RT * MT][64],
                                                  const bf16_t* __restrict__ x, long long ldx_,
                                                  const W* __restrict__ Wp, const float* __restrict__ wscale,
                                                  float* __restrict__ part, int N, int K, int S, int Mpad) {
-  constexpr int FP8 = kFp8<W>;
+  constexpr int FMT = kFp8<W>;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int s = blockIdx.y;
   const int KS = K >> 5;                      // k-steps of 32
@@ -224,7 +307,7 @@ __device__ __forceinline__ void skinny_gemm_body(float4v (&red)[3][RT * MT][64],
   // CU slots free for the concurrent decoder stream (see tune_fused_splits)
   for (int tg = blockIdx.x; tg < ngroups; tg += gridDim.x) {
     const int tile0 = tg * RT;                  // first 16-row tile
-    const W* wp = Wp + (size_t)tile0 * tile_stride + (size_t)lane * (FP8 ? 16 : 8);
+    const W* wp = Wp + (size_t)tile0 * tile_stride + (size_t)lane * (FMT ? 16 : 8);
     float4v acc[RT][MT];
 #pragma unroll
     for (int i = 0; i < RT; ++i)
@@ -232,7 +315,7 @@ __device__ __forceinline__ void skinny_gemm_body(float4v (&red)[3][RT * MT][64],
       for (int j = 0; j < MT; ++j) acc[i][j] = (float4v){0.f, 0.f, 0.f, 0.f};
 
     // ping-pong register prefetch over groups of U k-steps
-    Frag<RT, MT, U, FP8> f0, f1;
+    Frag<RT, MT, U, FMT> f0, f1;
     load_frag(f0, wp, tile_stride, xp, ldx_, ks0);
     stream_k(f0, f1, acc, wp, tile_stride, xp, ldx_, ks0, kw / U);
 
@@ -253,7 +336,7 @@ __device__ __forceinline__ void skinny_gemm_body(float4v (&red)[3][RT * MT][64],
           // C layout (16x16): col = lane&15 (token m), rows n = 4*(lane>>4) + reg
           const int m = j * 16 + (lane & 15);
           const int n = (tile0 + i) * 16 + 4 * (lane >> 4);
-          if constexpr (FP8) v *= *reinterpret_cast<const float4v*>(wscale + n);
+          if constexpr (FMT) v *= *reinterpret_cast<const float4v*>(wscale + n);
           *reinterpret_cast<float4v*>(part + ((size_t)s * Mpad + m) * N + n) = v;
         }
     }
@@ -388,8 +471,8 @@ __device__ __forceinline__ void store_xc(const XRegs<MP, U>& r, bf16_t* xs) {
   }
 }
 
-template <int RT, int MT, int U, int FP8>
-__device__ __forceinline__ void mma_xl(const WFrag<RT, U, FP8>& f, float4v (&acc)[RT][MT], const bf16_t* xs,
+template <int RT, int MT, int U, int FMT>
+__device__ __forceinline__ void mma_xl(const WFrag<RT, U, FMT>& f, float4v (&acc)[RT][MT], const bf16_t* xs,
                                        int lane) {
 #pragma unroll
   for (int u = 0; u < U; ++u) {
@@ -407,9 +490,9 @@ __device__ __forceinline__ void mma_xl(const WFrag<RT, U, FP8>& f, float4v (&acc
 // next chunk's x, then the next weight group (both unconditional, clamped to
 // the last chunk: no join point drains the prefetch, see stream_k), consume the
 // current chunk from LDS, then (barrier) overwrite LDS with the next chunk.
-template <int RT, int MT, int U, int FP8, typename W>
-__device__ __forceinline__ void stream_k_xl(WFrag<RT, U, FP8>& f0, WFrag<RT, U, FP8>& f1, XRegs<MT * 16, U>& xr,
-                                            float4v (&acc)[RT][MT], const W* wp,
+template <int RT, int MT, int U, int FMT, typename WP>
+__device__ __forceinline__ void stream_k_xl(WFrag<RT, U, FMT>& f0, WFrag<RT, U, FMT>& f1, XRegs<MT * 16, U>& xr,
+                                            float4v (&acc)[RT][MT], const WP wp,
                                             size_t tile_stride, const bf16_t* x, long long ldx_,
                                             bf16_t* xs, int ks0, int ng, int lane) {
   auto ks = [&](int g) { return ks0 + (g < ng ? g : ng - 1) * U; };
@@ -488,7 +571,8 @@ struct FusedParams {
   int rt;                 // output tile rows / 16 (1, 2; 4 at Mpad 64)
   int wr;                 // waves along the rows (1, or 4 with S == 1; any S with xl)
   int xl;                 // x through LDS (wr == 4; Mpad 32 / 64 / 128)
-  int wdtype;             // weight stream: 0 bf16 (Wp), 1 fp8 e4m3fn (Wp = Wp8 bytes + wscale)
+  int wdtype;             // weight stream: 0 bf16 (Wp), 1 fp8 e4m3fn (Wp = Wp8 bytes + wscale),
+                          // 2 MXFP4 (Wp = Wp4 nibble bytes, wscale = the e8m0 scale bytes Ws)
   const float* wscale;    // fp8: f32 [N] per-row dequantisation scale (rows in Wp order)
 };
 
@@ -503,7 +587,7 @@ struct FusedArgs {
   const int* positions; const float2* cs; bf16_t* q_out; bf16_t* kc; bf16_t* vc;
   const int* slots; int H, Hkv, D, blk;                                       // FEPI_ROPE
   int prio;                                     // s_setprio 3 for the launch (attn_decode.hip)
-  const float* wscale;                          // fp8 weight stream: per-row scale (else unused)
+  const float* wscale;                          // fp8 weight stream: per-row scale; MXFP4: the e8m0 bytes
 };
 
 // WR: waves along the rows. WR = 1: the 4 waves split the tile's K range
@@ -536,7 +620,7 @@ constexpr int SRED_SUM = 512, SRED_SCALE = 768, SRED_MEAN = 896;
 // acc[i][j][r] = C[16 * i + nq + r][16 * j + (lane & 15)], nq = 4 * (lane >> 4):
 // column = token, rows = 4 consecutive features per lane - the layout the
 // prompt-pass GEMMs (gemm_mfma.h) also produce.
-template <int RT, int MT, int U, int WR, int MODE, int NORM, int XL, int FP8 = 0>
+template <int RT, int MT, int U, int WR, int MODE, int NORM, int XL, int FMT = 0>
 __device__ __forceinline__ void skinny_fused_tile(const FusedArgs& a, float* smem, bf16_t* xs, const int bx,
                                                   const int by) {
   constexpr int WK = 4 / WR;                     // waves along K
@@ -553,17 +637,25 @@ __device__ __forceinline__ void skinny_fused_tile(const FusedArgs& a, float* sme
   const int KS = a.K >> 5;
   const int kw = KS / (a.S * WK);
   const int ks0 = (s * WK + wk) * kw;
-  const size_t tile_stride = (size_t)KS * 512;
-  typedef typename std::conditional<FP8 != 0, fp8_t, bf16_t>::type W;
-  const W* wp = reinterpret_cast<const W*>(a.Wp) + (size_t)(tile * RT) * tile_stride +
-                (size_t)lane * (FP8 ? 16 : 8);
+  // elements of W per 16-row tile (MXFP4: bytes of the nibble stream)
+  const size_t tile_stride = (size_t)KS * (FMT == WF_MXFP4 ? 256 : 512);
+  typedef typename std::conditional<FMT != 0, fp8_t, bf16_t>::type W;
+  const auto wp = [&]() {
+    const W* p = reinterpret_cast<const W*>(a.Wp) + (size_t)(tile * RT) * tile_stride +
+                 (size_t)lane * (FMT ? 16 : 8);
+    if constexpr (FMT == WF_MXFP4)   // a.wscale: the e8m0 scale stream
+      return Mx4Ptr{p, reinterpret_cast<const unsigned char*>(a.wscale) +
+                           (size_t)(tile * RT) * (tile_stride >> 4) + (size_t)(lane & 15) * 4};
+    else
+      return p;
+  }();
   const bf16_t* xp = a.x + (size_t)(lane & 15) * a.ldx + 8 * (lane >> 4);
 
   // the first weight group is requested before the norm prologue: the row
   // statistics only scale the accumulator, so the stream need not wait for
   // them (the prologue's two L2 round trips then hide under the first fill)
-  Frag<RT, MT, XL ? 1 : U, FP8> f0, f1;
-  WFrag<RT, XL ? U : 1, FP8> w0, w1;
+  Frag<RT, MT, XL ? 1 : U, FMT> f0, f1;
+  WFrag<RT, XL ? U : 1, FMT> w0, w1;
   XRegs<XL ? MT * 16 : 64, XL ? U : 1> xr;
   const int ng = kw / U;
   if constexpr (XL) {
@@ -624,7 +716,7 @@ __device__ __forceinline__ void skinny_fused_tile(const FusedArgs& a, float* sme
       for (int r = 0; r < 4; ++r) ecs[i][j][r] = make_float2(1.f, 0.f);
   }
   if (wk == 0) {
-    if constexpr (FP8) {
+    if constexpr (FMT == WF_FP8) {
 #pragma unroll
       for (int i = 0; i < RT; ++i)
         svec[i] = *reinterpret_cast<const float4*>(a.wscale + tile * (16 * RT) + i * 16 + nq);
@@ -814,8 +906,9 @@ __device__ __forceinline__ void skinny_fused_tile(const FusedArgs& a, float* sme
   // y = s * ((W g) x - mean * colsum) with colsum[n] = sum_k (W g)[n][k]; the
   // LayerNorm shift (W b) is folded into the bias.
   // fp8 weights: the K reduction is complete here (cross-wave and split-K), so
-  // the per-row dequantisation scale comes first
-  if constexpr (FP8) {
+  // the per-row dequantisation scale comes first (MXFP4: the block scales
+  // went into the A fragments, nothing is left to apply)
+  if constexpr (FMT == WF_FP8) {
 #pragma unroll
     for (int i = 0; i < RT; ++i) {
       const float4 sv = svec[i];
@@ -1014,9 +1107,21 @@ __global__ __launch_bounds__(256) void skinny_fused_fp8_kernel(FusedArgs a) {
   skinny_fused_tile<RT, MT, U, WR, MODE, NORM, XL, 1>(a, smem, xs, blockIdx.x, blockIdx.y);
 }
 
-template <int FP8, int RT, int MT, int U, int WR, int MODE, int NORM, int XL>
+// the MXFP4 weight stream, likewise
+template <int RT, int MT, int U, int WR, int MODE, int NORM, int XL = 0>
+__global__ __launch_bounds__(256) void skinny_fused_mxfp4_kernel(FusedArgs a) {
+  constexpr int SMF = FusedSmem<RT, MT, WR>::NSM + 4;
+  __shared__ __attribute__((aligned(16))) float smem[SMF];
+  __shared__ __attribute__((aligned(16))) bf16_t xs[XL ? U * MT * 16 * XROW : 8];
+  if (a.prio) __builtin_amdgcn_s_setprio(3);
+  skinny_fused_tile<RT, MT, U, WR, MODE, NORM, XL, WF_MXFP4>(a, smem, xs, blockIdx.x, blockIdx.y);
+}
+
+template <int FMT, int RT, int MT, int U, int WR, int MODE, int NORM, int XL>
 static void launch_fused_kernel(dim3 grid, const FusedArgs& a, hipStream_t st) {
-  if constexpr (FP8)
+  if constexpr (FMT == WF_MXFP4)
+    hipLaunchKernelGGL((skinny_fused_mxfp4_kernel<RT, MT, U, WR, MODE, NORM, XL>), grid, dim3(256), 0, st, a);
+  else if constexpr (FMT == WF_FP8)
     hipLaunchKernelGGL((skinny_fused_fp8_kernel<RT, MT, U, WR, MODE, NORM, XL>), grid, dim3(256), 0, st, a);
   else
     hipLaunchKernelGGL((skinny_fused_kernel<RT, MT, U, WR, MODE, NORM, XL>), grid, dim3(256), 0, st, a);
@@ -1028,27 +1133,30 @@ static void launch_fused_kernel(dim3 grid, const FusedArgs& a, hipStream_t st) {
 // 10-step range in one - measured slower in the pipeline, 3.51 -> 3.68 ms per
 // LLM step, and were removed: docs/KNOBS.md.)
 // (fp8: a 16-byte weight load spans two k-steps, so a wave's k range must be
-// even - K % (S * WK * 64) == 0 - and is rejected otherwise)
+// even - K % (S * WK * 64) == 0 - and is rejected otherwise. MXFP4: four
+// k-steps, K % (S * WK * 128) == 0; the layouts with groups of 2 k-steps take
+// the load in 8-byte halves)
 // WR = 4: one group size per layout. loqa_skinny_fused admits only
 // K % (S * 128) == 0, and WR = 4 without XL only S == 1, so a wave's k range
 // is a multiple of 4 k-steps and no smaller group is ever needed; the check
 // here keeps a caller that bypasses the entry point from reading past K.
 //   register form: at most 2 k-steps per group at Mpad 64 (VGPRs);
 //   XL: the group is one LDS chunk, 2 k-steps when the VGPR budget is tight.
-template <int RT, int MT, int WR, int XL, int MODE, int NORM, int FP8>
+template <int RT, int MT, int WR, int XL, int MODE, int NORM, int FMT>
 static int launch_fused(const FusedArgs& a, hipStream_t st) {
   constexpr int WK = 4 / WR;
   dim3 grid(a.N / (16 * RT * WR), a.S);
   const int kw = a.K / 32 / (a.S * WK);
+  if (FMT == WF_MXFP4 && kw % 4) return (int)hipErrorInvalidValue;
   if constexpr (WR == 4) {
     constexpr int U = XL ? (RT * MT >= 16 ? 2 : 4) : (MT <= 2 ? 4 : 2);
     if (kw % U) return (int)hipErrorInvalidValue;
-    launch_fused_kernel<FP8, RT, MT, U, 4, MODE, NORM, XL>(grid, a, st);
+    launch_fused_kernel<FMT, RT, MT, U, 4, MODE, NORM, XL>(grid, a, st);
   } else if (MT <= 2 && kw % 4 == 0) {   // Mpad 64: at most 2 k-steps per prefetch group (VGPRs)
-    launch_fused_kernel<FP8, RT, MT, (MT <= 2 ? 4 : 2), 1, MODE, NORM, 0>(grid, a, st);
+    launch_fused_kernel<FMT, RT, MT, (MT <= 2 ? 4 : 2), 1, MODE, NORM, 0>(grid, a, st);
   } else if (kw % 2 == 0) {
-    launch_fused_kernel<FP8, RT, MT, 2, 1, MODE, NORM, 0>(grid, a, st);
-  } else if constexpr (!FP8) {
+    launch_fused_kernel<FMT, RT, MT, 2, 1, MODE, NORM, 0>(grid, a, st);
+  } else if constexpr (!FMT) {
     launch_fused_kernel<0, RT, MT, 1, 1, MODE, NORM, 0>(grid, a, st);
   } else {
     return (int)hipErrorInvalidValue;
@@ -1064,51 +1172,51 @@ static int launch_fused(const FusedArgs& a, hipStream_t st) {
 // the activation tile is then re-read from L2 by half as many workgroups.
 // wr: waves along the rows (1 or 4; 4 only with S == 1, or with xl).
 // xl: x through LDS, Mpad 32 / 64 / 128, 4 waves along rows, any split-K.
-template <int MODE, int NORM, int FP8>
+template <int MODE, int NORM, int FMT>
 static int dispatch_shape(const FusedArgs& a, int rt, int wr, int xl, hipStream_t st) {
   auto is = [&](int mpad, int r, int w, int x) { return a.Mpad == mpad && rt == r && wr == w && !xl == !x; };
-  if (is(16, 1, 1, 0)) return launch_fused<1, 1, 1, 0, MODE, NORM, FP8>(a, st);
-  if (is(16, 1, 4, 0)) return launch_fused<1, 1, 4, 0, MODE, NORM, FP8>(a, st);
-  if (is(16, 2, 1, 0)) return launch_fused<2, 1, 1, 0, MODE, NORM, FP8>(a, st);
-  if (is(16, 2, 4, 0)) return launch_fused<2, 1, 4, 0, MODE, NORM, FP8>(a, st);
-  if (is(32, 1, 1, 0)) return launch_fused<1, 2, 1, 0, MODE, NORM, FP8>(a, st);
-  if (is(32, 1, 4, 0)) return launch_fused<1, 2, 4, 0, MODE, NORM, FP8>(a, st);
-  if (is(32, 2, 1, 0)) return launch_fused<2, 2, 1, 0, MODE, NORM, FP8>(a, st);
-  if (is(32, 2, 4, 0)) return launch_fused<2, 2, 4, 0, MODE, NORM, FP8>(a, st);
-  if (is(64, 1, 1, 0)) return launch_fused<1, 4, 1, 0, MODE, NORM, FP8>(a, st);
-  if (is(64, 1, 4, 0)) return launch_fused<1, 4, 4, 0, MODE, NORM, FP8>(a, st);
-  if (is(64, 2, 1, 0)) return launch_fused<2, 4, 1, 0, MODE, NORM, FP8>(a, st);
-  if (is(64, 2, 4, 0)) return launch_fused<2, 4, 4, 0, MODE, NORM, FP8>(a, st);
-  if (is(64, 4, 1, 0)) return launch_fused<4, 4, 1, 0, MODE, NORM, FP8>(a, st);
-  if (is(64, 4, 4, 0)) return launch_fused<4, 4, 4, 0, MODE, NORM, FP8>(a, st);
-  if (is(32, 1, 4, 1)) return launch_fused<1, 2, 4, 1, MODE, NORM, FP8>(a, st);
-  if (is(32, 2, 4, 1)) return launch_fused<2, 2, 4, 1, MODE, NORM, FP8>(a, st);
-  if (is(64, 1, 4, 1)) return launch_fused<1, 4, 4, 1, MODE, NORM, FP8>(a, st);
-  if (is(64, 2, 4, 1)) return launch_fused<2, 4, 4, 1, MODE, NORM, FP8>(a, st);
-  if (is(128, 1, 4, 1)) return launch_fused<1, 8, 4, 1, MODE, NORM, FP8>(a, st);
-  if (is(128, 2, 4, 1)) return launch_fused<2, 8, 4, 1, MODE, NORM, FP8>(a, st);
+  if (is(16, 1, 1, 0)) return launch_fused<1, 1, 1, 0, MODE, NORM, FMT>(a, st);
+  if (is(16, 1, 4, 0)) return launch_fused<1, 1, 4, 0, MODE, NORM, FMT>(a, st);
+  if (is(16, 2, 1, 0)) return launch_fused<2, 1, 1, 0, MODE, NORM, FMT>(a, st);
+  if (is(16, 2, 4, 0)) return launch_fused<2, 1, 4, 0, MODE, NORM, FMT>(a, st);
+  if (is(32, 1, 1, 0)) return launch_fused<1, 2, 1, 0, MODE, NORM, FMT>(a, st);
+  if (is(32, 1, 4, 0)) return launch_fused<1, 2, 4, 0, MODE, NORM, FMT>(a, st);
+  if (is(32, 2, 1, 0)) return launch_fused<2, 2, 1, 0, MODE, NORM, FMT>(a, st);
+  if (is(32, 2, 4, 0)) return launch_fused<2, 2, 4, 0, MODE, NORM, FMT>(a, st);
+  if (is(64, 1, 1, 0)) return launch_fused<1, 4, 1, 0, MODE, NORM, FMT>(a, st);
+  if (is(64, 1, 4, 0)) return launch_fused<1, 4, 4, 0, MODE, NORM, FMT>(a, st);
+  if (is(64, 2, 1, 0)) return launch_fused<2, 4, 1, 0, MODE, NORM, FMT>(a, st);
+  if (is(64, 2, 4, 0)) return launch_fused<2, 4, 4, 0, MODE, NORM, FMT>(a, st);
+  if (is(64, 4, 1, 0)) return launch_fused<4, 4, 1, 0, MODE, NORM, FMT>(a, st);
+  if (is(64, 4, 4, 0)) return launch_fused<4, 4, 4, 0, MODE, NORM, FMT>(a, st);
+  if (is(32, 1, 4, 1)) return launch_fused<1, 2, 4, 1, MODE, NORM, FMT>(a, st);
+  if (is(32, 2, 4, 1)) return launch_fused<2, 2, 4, 1, MODE, NORM, FMT>(a, st);
+  if (is(64, 1, 4, 1)) return launch_fused<1, 4, 4, 1, MODE, NORM, FMT>(a, st);
+  if (is(64, 2, 4, 1)) return launch_fused<2, 4, 4, 1, MODE, NORM, FMT>(a, st);
+  if (is(128, 1, 4, 1)) return launch_fused<1, 8, 4, 1, MODE, NORM, FMT>(a, st);
+  if (is(128, 2, 4, 1)) return launch_fused<2, 8, 4, 1, MODE, NORM, FMT>(a, st);
   return (int)hipErrorInvalidValue;
 }
 
-// fp8 weights: NORM_NONE and NORM_RMS only (the Llama decode), LayerNorm is rejected
-template <int MODE, int FP8>
+// fp8 / MXFP4 weights: NORM_NONE and NORM_RMS only (the Llama decode), LayerNorm is rejected
+template <int MODE, int FMT>
 static int dispatch_norm(const FusedArgs& a, int norm, int rt, int wr, int xl, hipStream_t st) {
   switch (norm) {
-    case NORM_NONE: return dispatch_shape<MODE, NORM_NONE, FP8>(a, rt, wr, xl, st);
-    case NORM_RMS: return dispatch_shape<MODE, NORM_RMS, FP8>(a, rt, wr, xl, st);
+    case NORM_NONE: return dispatch_shape<MODE, NORM_NONE, FMT>(a, rt, wr, xl, st);
+    case NORM_RMS: return dispatch_shape<MODE, NORM_RMS, FMT>(a, rt, wr, xl, st);
     case NORM_LN:
-      if constexpr (!FP8) return dispatch_shape<MODE, NORM_LN, 0>(a, rt, wr, xl, st);
+      if constexpr (!FMT) return dispatch_shape<MODE, NORM_LN, 0>(a, rt, wr, xl, st);
     default: return (int)hipErrorInvalidValue;
   }
 }
 
-template <int FP8>
+template <int FMT>
 static int dispatch_mode(const FusedArgs& a, int mode, int norm, int rt, int wr, int xl, hipStream_t st) {
   switch (mode) {
-    case FEPI_SILU: return dispatch_norm<FEPI_SILU, FP8>(a, norm, rt, wr, xl, st);
-    case FEPI_RESID: return dispatch_norm<FEPI_RESID, FP8>(a, norm, rt, wr, xl, st);
-    case FEPI_ROPE: return dispatch_norm<FEPI_ROPE, FP8>(a, norm, rt, wr, xl, st);
-    case FEPI_ACT: return dispatch_norm<FEPI_ACT, FP8>(a, norm, rt, wr, xl, st);
+    case FEPI_SILU: return dispatch_norm<FEPI_SILU, FMT>(a, norm, rt, wr, xl, st);
+    case FEPI_RESID: return dispatch_norm<FEPI_RESID, FMT>(a, norm, rt, wr, xl, st);
+    case FEPI_ROPE: return dispatch_norm<FEPI_ROPE, FMT>(a, norm, rt, wr, xl, st);
+    case FEPI_ACT: return dispatch_norm<FEPI_ACT, FMT>(a, norm, rt, wr, xl, st);
     default: return (int)hipErrorInvalidValue;
   }
 }

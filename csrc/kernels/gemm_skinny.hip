@@ -1,6 +1,6 @@
 // Decode-shaped GEMM entry points and the bf16 weight stream's kernel
 // instances (kernels and launch templates: gemm_skinny.h; the fp8 weight
-// stream's instances: gemm_skinny_fp8.hip).
+// stream's instances: gemm_skinny_fp8.hip; the MXFP4 one's: gemm_skinny_mxfp4.hip).
 #include "gemm_skinny.h"
 
 // x: [Mpad, >=K] bf16 (row stride ldx), rows >= M must be finite (zeros);
@@ -78,6 +78,9 @@ static FusedArgs fused_args(const FusedParams& p) {
 // the fp8 weight stream's instances (gemm_skinny_fp8.hip)
 int loqa_skinny_fused_fp8_launch(const FusedArgs& a, int mode, int norm, int rt, int wr, int xl,
                                  hipStream_t st);
+// the MXFP4 weight stream's instances (gemm_skinny_mxfp4.hip)
+int loqa_skinny_fused_mxfp4_launch(const FusedArgs& a, int mode, int norm, int rt, int wr, int xl,
+                                   hipStream_t st);
 
 // mode: 1 silu (out [Mpad, ldo >= N/2]), 2 residual (+bias) + row sum-of-squares
 // (+ row sums), 3 (RoPE if cs) + paged KV append + q, 4 act(bias + x W^T) -> out
@@ -89,6 +92,10 @@ int loqa_skinny_fused_fp8_launch(const FusedArgs& a, int mode, int norm, int rt,
 // wdtype 1: Wp holds e4m3fn bytes in the fp8 fragment order with the per-row
 // scale wscale; no LayerNorm, and every wave's k range must be a whole number
 // of 64-wide k-step pairs (K % (S * waves-along-K * 64) == 0).
+// wdtype 2: Wp holds MXFP4 nibble bytes in their fragment order and wscale the
+// e8m0 scale bytes (one per row and k-step); no LayerNorm, and every wave's k
+// range must be a whole number of 128-wide loads
+// (K % (S * waves-along-K * 128) == 0).
 extern "C" int loqa_skinny_fused(const FusedParams* p, hipStream_t st) {
   const int Mpad = p->Mpad, N = p->N, K = p->K, S = p->S;
   if (S < 1 || K % (S * 128) || p->ldx % 8 || N % 32 ||
@@ -107,12 +114,17 @@ extern "C" int loqa_skinny_fused(const FusedParams* p, hipStream_t st) {
   if (p->mode == FEPI_RESID && (!p->residual || !p->rowsq_out)) return (int)hipErrorInvalidValue;
   if (p->wr != 1 && (p->wr != 4 || (S != 1 && !p->xl) || N % (64 * p->rt)))
     return (int)hipErrorInvalidValue;
-  if (p->wdtype != 0 && p->wdtype != 1) return (int)hipErrorInvalidValue;
+  if (p->wdtype < 0 || p->wdtype > 2) return (int)hipErrorInvalidValue;
+  if (p->wdtype == 2 &&
+      (!p->wscale || p->norm == NORM_LN || K % (S * (p->wr == 4 ? 1 : 4) * 128)))
+    return (int)hipErrorInvalidValue;
   if (p->wdtype == 1 &&
       (!p->wscale || p->norm == NORM_LN || K % (S * (p->wr == 4 ? 1 : 4) * 64)))
     return (int)hipErrorInvalidValue;
   const FusedArgs a = fused_args(*p);
   if (p->wdtype == 1)
     return loqa_skinny_fused_fp8_launch(a, p->mode, p->norm, p->rt, p->wr, p->xl, st);
+  if (p->wdtype == 2)
+    return loqa_skinny_fused_mxfp4_launch(a, p->mode, p->norm, p->rt, p->wr, p->xl, st);
   return dispatch_mode<0>(a, p->mode, p->norm, p->rt, p->wr, p->xl, st);
 }

@@ -199,8 +199,10 @@ class GPUConfig:
     kv_block: int = 16
     max_seq_len: int = 1024
     llm_backend: str = "gpu"          # gpu | ollama
-    # LLM projection / lm_head weights: bf16, or fp8 (e4m3 weight streams with
-    # per-row scales: half the bytes per decode step; one GPU, gpu backend)
+    # LLM projection / lm_head weights: bf16, fp8 (e4m3 weight streams with
+    # per-row scales: half the bytes per decode step; one GPU, gpu backend) or
+    # mxfp4 (projections as e2m1 with a power-of-two scale per 32 weights, 4.25
+    # bits per weight, the lm_head as fp8; one GPU, gpu backend)
     llm_weights: str = "bf16"
     stt_backend: str = "gpu"          # gpu | http
     # the transcript's confidence: "heuristic" (the reference's text rules) or
@@ -311,14 +313,15 @@ class Config:
             raise ConfigError(f"invalid ARBITRATION_SCOPE: {self.arbitration.scope}")
         if self.gpu.tp < 1:
             raise ConfigError(f"HUB_TP must be >= 1: {self.gpu.tp}")
-        if self.gpu.llm_weights not in ("bf16", "fp8"):
-            raise ConfigError(f"invalid HUB_LLM_WEIGHTS (bf16 | fp8): {self.gpu.llm_weights}")
-        if self.gpu.llm_weights == "fp8":
+        if self.gpu.llm_weights not in ("bf16", "fp8", "mxfp4"):
+            raise ConfigError(f"invalid HUB_LLM_WEIGHTS (bf16 | fp8 | mxfp4): {self.gpu.llm_weights}")
+        if self.gpu.llm_weights != "bf16":
+            wd = self.gpu.llm_weights
             if self.gpu.tp > 1:
-                raise ConfigError("HUB_LLM_WEIGHTS=fp8 needs HUB_TP=1 (no tensor-parallel fp8 "
+                raise ConfigError(f"HUB_LLM_WEIGHTS={wd} needs HUB_TP=1 (no tensor-parallel {wd} "
                                   f"shards): HUB_TP={self.gpu.tp}")
             if self.gpu.llm_backend != "gpu":
-                raise ConfigError("HUB_LLM_WEIGHTS=fp8 needs HUB_LLM_BACKEND=gpu: "
+                raise ConfigError(f"HUB_LLM_WEIGHTS={wd} needs HUB_LLM_BACKEND=gpu: "
                                   f"{self.gpu.llm_backend}")
         if self.gpu.stt_confidence not in ("heuristic", "acoustic"):
             raise ConfigError("invalid HUB_STT_CONFIDENCE (heuristic | acoustic): "

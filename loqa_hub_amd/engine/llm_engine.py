@@ -86,17 +86,21 @@ class LLMEngine:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.tp = tp or TPGroup()
         # "fp8": every projection and the lm_head as e4m3 weight streams (half
-        # the bytes per decode step; implies the compact single-copy layout)
-        if weight_dtype not in ("bf16", "fp8"):
-            raise ValueError(f"weight_dtype must be 'bf16' or 'fp8', got {weight_dtype!r}")
-        if weight_dtype == "fp8":
+        # the bytes per decode step; implies the compact single-copy layout).
+        # "mxfp4": the projections as MXFP4 streams (4.25 bits per weight), the
+        # lm_head as fp8; otherwise like "fp8"
+        if weight_dtype not in ("bf16", "fp8", "mxfp4"):
+            raise ValueError(f"weight_dtype must be 'bf16', 'fp8' or 'mxfp4', got {weight_dtype!r}")
+        if weight_dtype != "bf16":
+            wd = weight_dtype
             if self.tp.world > 1:
-                raise ValueError("weight_dtype='fp8' is single-GPU only (no tensor-parallel fp8 shards)")
+                raise ValueError(f"weight_dtype='{wd}' is single-GPU only (no tensor-parallel {wd} shards)")
             if not fused_decode:
-                raise ValueError("weight_dtype='fp8' needs fused_decode=True (fp8 weights exist "
+                raise ValueError(f"weight_dtype='{wd}' needs fused_decode=True ({wd} weights exist "
                                  "only in the fused decode layout)")
-            if weights is not None and getattr(weights, "weight_dtype", "bf16") != "fp8":
-                raise ValueError("weight_dtype='fp8' but the given weights are bf16")
+            if weights is not None and getattr(weights, "weight_dtype", "bf16") != wd:
+                raise ValueError(f"weight_dtype='{wd}' but the given weights are "
+                                 f"{getattr(weights, 'weight_dtype', 'bf16')}")
         elif weights is not None:
             weight_dtype = getattr(weights, "weight_dtype", "bf16")
         self.weight_dtype = weight_dtype

@@ -122,8 +122,12 @@ class LlamaWeights:
         # per-row scale (ops.Fp8Weight) - half the bytes read per decode step,
         # half the resident weights. Implies ``compact``; the embedding table,
         # the norms, the KV cache and cos_sin stay bf16 / f32.
+        # "mxfp4": the four projections are MXFP4 streams (ops.Mxfp4Weight: e2m1
+        # with a power-of-two scale per 32 weights of a row, 4.25 bits per
+        # weight); the lm_head, which picks among the grammar's candidates,
+        # stays an fp8 stream. Otherwise as "fp8".
         self.weight_dtype = self._check_weight_dtype(weight_dtype, tp)
-        compact = compact or weight_dtype == "fp8"
+        compact = compact or weight_dtype in ("fp8", "mxfp4")
         # compact: ONE copy of every projection, in the fused decode layout
         # (prefill then runs through the fused GEMMs in <= 64-token chunks).
         # Llama-3-70B bf16 (141 GB) fits one 288 GB MI355X this way, and a
@@ -184,16 +188,21 @@ class LlamaWeights:
 
     @staticmethod
     def _check_weight_dtype(weight_dtype: str, tp: TPGroup) -> str:
-        if weight_dtype not in ("bf16", "fp8"):
-            raise ValueError(f"weight_dtype must be 'bf16' or 'fp8', got {weight_dtype!r}")
-        if weight_dtype == "fp8" and tp.world > 1:
-            raise ValueError("weight_dtype='fp8' is single-GPU only (no tensor-parallel fp8 shards)")
+        if weight_dtype not in ("bf16", "fp8", "mxfp4"):
+            raise ValueError(f"weight_dtype must be 'bf16', 'fp8' or 'mxfp4', got {weight_dtype!r}")
+        if weight_dtype != "bf16" and tp.world > 1:
+            raise ValueError(f"weight_dtype='{weight_dtype}' is single-GPU only "
+                             f"(no tensor-parallel {weight_dtype} shards)")
         return weight_dtype
 
-    def _pack(self, w: torch.Tensor):
+    def _pack(self, w: torch.Tensor, head: bool = False):
         """A row-major projection -> its decode-GEMM operand: fragment-ordered
-        bf16, or (fp8) quantised per row, then fragment-ordered."""
-        if getattr(self, "weight_dtype", "bf16") == "fp8":
+        bf16, or (fp8) quantised per row, or (mxfp4) per block of 32, then
+        fragment-ordered. ``head``: the lm_head, fp8 under "mxfp4" too."""
+        wd = getattr(self, "weight_dtype", "bf16")
+        if wd == "mxfp4" and not head:
+            return ops.quantize_weight_mxfp4(w.contiguous())
+        if wd in ("fp8", "mxfp4"):
             return ops.quantize_weight_fp8(w.contiguous())
         return ops.shuffle_weight(w.contiguous())
 
@@ -239,7 +248,7 @@ class LlamaWeights:
         pad = -w.shape[0] % 64
         if pad:
             w = torch.cat([w, torch.zeros(pad, w.shape[1], dtype=w.dtype, device=w.device)])
-        return self._pack(w)
+        return self._pack(w, head=True)
 
     @classmethod
     def from_tensors(cls, cfg: LlamaConfig, device, *, embed, layers: list[dict], final_norm,
@@ -248,7 +257,7 @@ class LlamaWeights:
         """Weights from explicit tensors (checkpoint loaders): ``layers`` hold
         attn_norm / wqkv (q|k|v rows) / wo / mlp_norm / w_gate_up (gate|up rows)
         / w_down. Unsharded tensors; ``tp`` > 1 shards them (Megatron split).
-        ``weight_dtype`` "fp8": the compact fp8 layout, converted layer by layer
+        ``weight_dtype`` "fp8" / "mxfp4": the compact quantised layout, converted layer by layer
         (``layers`` is emptied of its row-major projections as it goes)."""
         self = cls.__new__(cls)
         self.cfg, self.tp = cfg, TPGroup()
@@ -263,7 +272,7 @@ class LlamaWeights:
         if tp is not None and tp.world > 1:
             self.decode_layers, self.lm_head_p = [], None
             return cls.shard(self, tp)
-        if weight_dtype == "fp8":
+        if weight_dtype in ("fp8", "mxfp4"):
             self.compact = True
             self.decode_layers = []
             for i, L in enumerate(layers):
@@ -359,6 +368,8 @@ class LlamaWeights:
             nonlocal total
             if isinstance(t, ops.Fp8Weight):
                 add(t.wp); add(t.scale)
+            elif isinstance(t, ops.Mxfp4Weight):
+                add(t.wp); add(t.scales)
             elif isinstance(t, torch.Tensor):
                 key = t.untyped_storage().data_ptr()
                 if key not in seen:

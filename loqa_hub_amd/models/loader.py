@@ -89,10 +89,11 @@ def llama_state_dict(w: LlamaWeights) -> dict[str, torch.Tensor]:
 
 def llama_from_state_dict(cfg: LlamaConfig, sd: dict[str, torch.Tensor], device,
                           tp: TPGroup | None = None, weight_dtype: str = "bf16") -> LlamaWeights:
-    """``weight_dtype`` "fp8": the checkpoint is served from e4m3 weight streams
+    """``weight_dtype`` "fp8" / "mxfp4": the checkpoint is served from quantised
+    weight streams
     (``LlamaWeights.from_tensors`` converts layer by layer; the per-projection
     tensors leave ``sd`` here, so each row-major layer is freed once converted)."""
-    take = sd.pop if weight_dtype == "fp8" else sd.__getitem__
+    take = sd.pop if weight_dtype in ("fp8", "mxfp4") else sd.__getitem__
     layers = []
     for i in range(cfg.n_layers):
         p = f"model.layers.{i}."

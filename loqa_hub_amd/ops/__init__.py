@@ -609,7 +609,8 @@ def tune_fused_splits(key: tuple, run, K: int, reps: int = 8, rts=(2,), ncopies:
     "also" (add the x-through-LDS layouts, any split) or "only" (Mpad 128).
     Returns (split-K, rt, wr) or (split-K, rt, 4, 1) for an XL layout.
     ``key`` = (mode, N, K, Mpad), with "fp8" appended for an fp8 weight stream
-    (a wave's k range is then a whole number of 64-wide k-step pairs)."""
+    (a wave's k range is then a whole number of 64-wide k-step pairs) or
+    "mxfp4" for an MXFP4 one (of 128-wide loads: K % (S * waves-along-K * 128) == 0)."""
     if key in _FSPLITS:
         return _FSPLITS[key]
     ov = _fsplit_override(key)
@@ -617,14 +618,16 @@ def tune_fused_splits(key: tuple, run, K: int, reps: int = 8, rts=(2,), ncopies:
         _FSPLITS[key] = ov
         return ov
     N = key[1]
-    kq = 64 if len(key) > 4 else 32      # k granule of one weight load
+    kq = _KGRANULE[tuple(key[4:])]       # k granule of one weight load
     cands = [] if xl == "only" else \
         [(s, rt, 1) for rt in rts for s in SPLIT_CANDIDATES if K % (s * 4 * kq) == 0]
-    if wr4 and xl != "only":
+    # (MXFP4 at K < 512, where no split of the 4-waves-along-K form holds whole
+    # loads, has the rows-per-wave layouts only)
+    if (wr4 or (kq == 128 and not cands)) and xl != "only":
         cands += [(1, rt, 4) for rt in rts if N % (64 * rt) == 0 and K % kq == 0]
     if xl != "no":
         cands += [(s, rt, 4, 1) for rt in (1, 2) for s in SPLIT_CANDIDATES
-                  if K % (s * 128) == 0 and N % (64 * rt) == 0]
+                  if K % (s * 128) == 0 and N % (64 * rt) == 0]   # >= every format's granule
     # co-scheduling cap: the STT and LLM decoders run concurrently on their own
     # streams; a grid that fills every CU slot makes the other stream's small
     # latency-bound kernels wait for it to drain (measured: a 768-workgroup
@@ -707,7 +710,8 @@ def graph_time(fn, reps: int = 8, trials: int = 3) -> float:
 
 def choose_splits(N: int, K: int, Mpad: int, target_wgs: int = 512, tag: tuple = ()) -> int:
     """Split-K factor: the tuned value if available, else enough splits for
-    >= ~2 workgroups per CU (256 CUs). ``tag`` = ("fp8",) for an fp8 weight."""
+    >= ~2 workgroups per CU (256 CUs). ``tag`` = ("fp8",) for an fp8 weight,
+    ("mxfp4",) for an MXFP4 one (the 4 waves along K each take whole loads)."""
     tuned = _SPLITS.get((N, K, Mpad) + tag)
     if tuned is not None:
         return tuned
@@ -715,7 +719,7 @@ def choose_splits(N: int, K: int, Mpad: int, target_wgs: int = 512, tag: tuple =
     tiles = max(1, N // (16 * rt))
     best = 1
     for s in SPLIT_CANDIDATES:
-        if K % (s * (256 if tag else 128)) != 0:
+        if K % (s * 4 * _KGRANULE[tag]) != 0:
             continue
         best = s
         if tiles * s >= target_wgs:
@@ -781,10 +785,59 @@ class Fp8Weight:
         return Fp8Weight(self.wp.to(device), self.scale.to(device), self.N, self.K)
 
 
+class Mxfp4Weight:
+    """A fused decode GEMM weight as an OCP MXFP4 stream: ``wp`` uint8
+    [N/16, K/128, 64, 16], e2m1 nibbles in the kernels' fragment order, and
+    ``scales`` uint8 [N/16, K/128, 16, 4], one e8m0 byte per row and block of
+    32 k values (``ref.shuffle_mxfp4``). 4.25 bits per weight. Stands in for a
+    shuffled bf16 weight wherever the fused decode GEMMs take one (``shape`` as
+    for ``Fp8Weight``); the plain ``skinny_gemm`` has no MXFP4 form."""
+
+    def __init__(self, wp: torch.Tensor, scales: torch.Tensor, N: int, K: int):
+        assert wp.dtype == torch.uint8 and wp.shape == (N // 16, K // 128, 64, 16)
+        assert scales.dtype == torch.uint8 and scales.shape == (N // 16, K // 128, 16, 4)
+        self.wp, self.scales, self.N, self.K = wp, scales, N, K
+
+    shape = property(lambda self: (self.N // 16, self.K // 32, 64, 8))
+    device = property(lambda self: self.wp.device)
+    is_cuda = property(lambda self: self.wp.is_cuda)
+    nbytes = property(lambda self: self.wp.numel() + self.scales.numel())
+
+    def numel(self) -> int:
+        return self.wp.numel() + self.scales.numel()
+
+    def element_size(self) -> int:
+        return 1
+
+    def clone(self) -> "Mxfp4Weight":
+        return Mxfp4Weight(self.wp.clone(), self.scales.clone(), self.N, self.K)
+
+    def to(self, device) -> "Mxfp4Weight":
+        return Mxfp4Weight(self.wp.to(device), self.scales.to(device), self.N, self.K)
+
+
+# k values per 16-byte lane load of a weight stream: a wave's k range is a
+# whole number of them
+_KGRANULE = {(): 32, ("fp8",): 64, ("mxfp4",): 128}
+
+
 def _wtag(wp) -> tuple:
     """Suffix of the tuning-cache keys of a weight: () for bf16 (the keys are
-    what they always were), ("fp8",) for an fp8 stream."""
+    what they always were), ("fp8",) for an fp8 stream, ("mxfp4",) for MXFP4."""
+    if isinstance(wp, Mxfp4Weight):
+        return ("mxfp4",)
     return ("fp8",) if isinstance(wp, Fp8Weight) else ()
+
+
+def quantize_weight_mxfp4(w: torch.Tensor) -> Mxfp4Weight:
+    """[N, K] bf16 (rows already norm-folded and permuted) -> ``Mxfp4Weight``:
+    per block of 32 k values the smallest power-of-two scale that clips
+    nothing, e2m1 codes rounded to nearest even (``ref.quantize_mxfp4_rows``),
+    in fragment order. Load time only."""
+    N, K = w.shape
+    assert N % 16 == 0 and K % 128 == 0, "MXFP4 weights need N % 16 == 0 and K % 128 == 0"
+    code, scales = ref.quantize_mxfp4_rows(w)
+    return Mxfp4Weight(*ref.shuffle_mxfp4(code, scales), N, K)
 
 
 def quantize_weight_fp8(w: torch.Tensor) -> Fp8Weight:
@@ -809,6 +862,8 @@ def skinny_gemm(x: torch.Tensor, wp, splits: int | None = None,
     if not _gpu(x):
         return ref.skinny_gemm(x, wp, S)
     assert Mpad in MPADS and x.dtype == torch.bfloat16 and x.stride(1) == 1
+    if isinstance(wp, Mxfp4Weight):
+        raise TypeError("skinny_gemm has no MXFP4 kernel (fused decode GEMMs only)")
     part = torch.empty(S, Mpad, N, dtype=torch.float32, device=x.device)
     if isinstance(wp, Fp8Weight):
         assert wp.is_cuda and wp.wp.is_contiguous() and wp.scale.is_contiguous()
@@ -1348,7 +1403,7 @@ def skinny_fused(x: torch.Tensor, wp, mode: str, scratch: FusedScratch, *,
     Mpad, K = x.shape
     N = wp.shape[0] * 16
     nrm = _NORMS[norm]
-    fp8 = isinstance(wp, Fp8Weight)
+    fp8, mx4 = isinstance(wp, Fp8Weight), isinstance(wp, Mxfp4Weight)
     tuned = _FSPLITS.get((mode, N, K, Mpad) + _wtag(wp))
     S = splits or (tuned[0] if tuned else choose_splits(N, K, Mpad, tag=_wtag(wp)))
     rt = rt or (tuned[1] if tuned else (1 if Mpad == 128 else 2))
@@ -1356,6 +1411,11 @@ def skinny_fused(x: torch.Tensor, wp, mode: str, scratch: FusedScratch, *,
         xl = tuned[3] if (tuned and not splits and len(tuned) > 3) else int(Mpad == 128)
     if wr is None:
         wr = tuned[2] if (tuned and not splits and len(tuned) > 2) else 1
+        if mx4 and wr == 1 and not xl and K % (S * 512):
+            # untuned MXFP4, K not a whole number of loads for 4 waves along K:
+            # the rows-per-wave layout takes any K % 128 == 0
+            S, wr = 1, 4
+            rt = rt if N % (64 * rt) == 0 else 1
     if xl:
         wr = 4
         rt = rt if rt in (1, 2) and N % (64 * rt) == 0 else 1
@@ -1384,6 +1444,10 @@ def skinny_fused(x: torch.Tensor, wp, mode: str, scratch: FusedScratch, *,
     if fp8:
         assert nrm != 2, "fp8 weights: no LayerNorm prologue"
         assert wp.is_cuda and wp.wp.is_contiguous() and wp.scale.is_contiguous()
+    elif mx4:
+        assert nrm != 2, "MXFP4 weights: no LayerNorm prologue"
+        assert wp.is_cuda and wp.wp.is_contiguous() and wp.scales.is_contiguous()
+        assert wp.wp.data_ptr() % 16 == 0 and wp.scales.data_ptr() % 4 == 0
     else:
         _bf16_contig(wp, "wp")
     if bias is not None:
@@ -1399,10 +1463,12 @@ def skinny_fused(x: torch.Tensor, wp, mode: str, scratch: FusedScratch, *,
     part = torch.empty(S, Mpad, N, dtype=torch.float32, device=x.device) if S > 1 else None
     blk = k_cache.shape[2] if k_cache is not None else 0
     p = FusedParams()
-    p.x, p.ldx, p.Wp, p.part, p.counters = ptr(x), x.stride(0), ptr(wp.wp if fp8 else wp), \
+    p.x, p.ldx, p.Wp, p.part, p.counters = ptr(x), x.stride(0), ptr(wp.wp if fp8 or mx4 else wp), \
         ptr(part), ptr(scratch.counters)
     if fp8:
         p.wdtype, p.wscale = 1, ptr(wp.scale)
+    elif mx4:
+        p.wdtype, p.wscale = 2, ptr(wp.scales)
     p.Mpad, p.N, p.K, p.S, p.mode, p.norm = Mpad, N, K, S, m, nrm
     if nrm:
         p.rowsq_in, p.rowsum_in = ptr(scratch.rowsq), ptr(scratch.rowsum)

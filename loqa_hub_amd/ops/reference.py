@@ -342,7 +342,78 @@ def dequant_fp8(weight):
     return q.float() * weight.scale.float()[:, None]
 
 
+E2M1_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)   # code & 7 -> magnitude; bit 3 is the sign
+MXFP4_BLOCK = 32                   # k values per e8m0 scale: one MFMA k-step
+# e8m0 scale bytes the quantiser emits: 2^(b - 127) for b in [2, 252], so the
+# smallest non-zero product 0.5 * 2^-125 and the largest 6 * 2^125 are normal
+# bf16 values. (0 shifted into an f32 exponent is 0.0, not 2^-127; 255 is NaN.)
+MXFP4_SCALE_MIN, MXFP4_SCALE_MAX = 2, 252
+
+
+def quantize_mxfp4_rows(w):
+    """OCP MXFP4 quantisation of w [N, K] (K % 32 == 0): (codes uint8 [N, K],
+    one e2m1 code 0..15 per element; scales uint8 [N, K/32], e8m0). Per block
+    of 32 the scale is the smallest power of two with amax / scale <= 6 (nothing
+    clips; 1 for an all-zero block, whose codes are +0), its exponent clamped to
+    [-125, 125]; elements round to the nearest grid point, ties to the even
+    code."""
+    N, K = w.shape
+    wf = w.float().reshape(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = wf.abs().amax(2)
+    # amax = m * 2^e with m in [0.5, 1): amax / 2^(e - 2) = 4m in [2, 4) <= 6, and
+    # one power less (8m) fits only while m <= 0.75
+    m, e = torch.frexp(amax)
+    e = torch.where(m <= 0.75, e - 3, e - 2)
+    e = torch.where(amax > 0, e, torch.zeros_like(e)).clamp(MXFP4_SCALE_MIN - 127, MXFP4_SCALE_MAX - 127)
+    v = (wf * torch.exp2(-e.float())[..., None]).abs().clamp(max=6.0)   # exact: a power of two
+    # round to nearest on {0, .5, 1, 1.5 | 2, 3 | 4, 6}: the spacing doubles at 2
+    # and at 4; torch.round is half-to-even, and an even multiple of the
+    # spacing is an even code in each segment
+    step = torch.where(v < 2, torch.full_like(v, 0.5), torch.where(v < 4, torch.ones_like(v),
+                                                                    torch.full_like(v, 2.0)))
+    r = torch.round(v / step) * step
+    grid = torch.tensor(E2M1_GRID, device=w.device)
+    code = torch.bucketize(r, grid).to(torch.uint8)         # r is a grid point: its index
+    code = code | ((wf < 0) & (r > 0)).to(torch.uint8) << 3
+    return code.reshape(N, K), (e + 127).to(torch.uint8)
+
+
+def shuffle_mxfp4(code, scales):
+    """codes [N, K] and e8m0 bytes [N, K/32] -> (wp uint8 [N/16, K/128, 64, 16],
+    ws uint8 [N/16, K/128, 16, 4]) in the kernels' order: lane l holds row
+    (l & 15); its bytes 4j..4j+3 are the 8 k values at offset 8 * (l >> 4) of
+    k-step 4g + j, ascending, two per byte with the even k in the low nibble.
+    ws[t, g, r, j] is the scale of row 16 t + r, k-step 4g + j."""
+    N, K = code.shape
+    b = code.reshape(N, K // 2, 2)
+    b = b[..., 0] | (b[..., 1] << 4)                                   # [N, K/2]
+    wp = b.reshape(N // 16, 16, K // 128, 4, 4, 4).permute(0, 2, 4, 1, 3, 5).contiguous().reshape(
+        N // 16, K // 128, 64, 16)
+    ws = scales.reshape(N // 16, 16, K // 128, 4).permute(0, 2, 1, 3).contiguous()
+    return wp, ws
+
+
+def unshuffle_mxfp4(wp, ws):
+    """Inverse of ``shuffle_mxfp4``: (codes uint8 [N, K], scales uint8 [N, K/32])."""
+    T, G = wp.shape[:2]
+    b = wp.reshape(T, G, 4, 16, 4, 4).permute(0, 3, 1, 4, 2, 5).reshape(T * 16, G * 64)
+    code = torch.stack([b & 15, b >> 4], -1).reshape(T * 16, G * 128)
+    return code, ws.permute(0, 2, 1, 3).reshape(T * 16, G * 4)
+
+
+def dequant_mxfp4(weight):
+    """f32 [N, K] = e2m1 * 2^(e8m0 - 127) of an MXFP4 weight container
+    (``ops.Mxfp4Weight``), by table: what the kernels' in-register convert
+    must reproduce bit for bit."""
+    code, sc = unshuffle_mxfp4(weight.wp, weight.scales)
+    grid = torch.tensor(E2M1_GRID + tuple(-g for g in E2M1_GRID), device=code.device)
+    v = grid[code.long()]
+    return v * torch.exp2(sc.float() - 127.0).repeat_interleave(MXFP4_BLOCK, 1)
+
+
 def unshuffle_weight(wp):
+    if hasattr(wp, "scales"):     # MXFP4 container: the dequantised rows (f32)
+        return dequant_mxfp4(wp)
     if hasattr(wp, "scale"):      # fp8 container: the dequantised rows (f32)
         return dequant_fp8(wp)
     T, KS = wp.shape[:2]

@@ -361,12 +361,12 @@ def main() -> int:
                     help="TP ranks share cuda:0 (spawned here when not under torchrun)")
     ap.add_argument("--compact", action="store_true",
                     help="TP: single-copy fused weights (needed when ranks share a GPU)")
-    ap.add_argument("--weights", choices=["bf16", "fp8"], default="bf16",
-                    help="configs 2 / 5, --tp 1: LLM projection weights (fp8: e4m3 weight streams, "
-                         "a secondary figure, never the headline)")
+    ap.add_argument("--weights", choices=["bf16", "fp8", "mxfp4"], default="bf16",
+                    help="configs 2 / 5, --tp 1: LLM projection weights (fp8: e4m3 weight streams; "
+                         "mxfp4: 4-bit projections, fp8 lm_head; secondary figures, never the headline)")
     args = ap.parse_args()
-    if args.weights == "fp8" and args.tp > 1:
-        ap.error("--weights fp8 is single-GPU only (--tp 1)")
+    if args.weights != "bf16" and args.tp > 1:
+        ap.error(f"--weights {args.weights} is single-GPU only (--tp 1)")
     if args.tp > 1:
         if args.config != [5]:
             ap.error("--tp applies to --config 5 only")

@@ -1,4 +1,5 @@
-"""Decode GEMMs on cold weights, bf16 against the fp8 (e4m3) weight stream.
+"""Decode GEMMs on cold weights, bf16 against the fp8 (e4m3) and the MXFP4
+(e2m1 + a scale byte per 32 weights) weight streams.
 
 For each Llama-3-8B / 70B decode shape and Mpad 16 / 64 the tuner of the
 engine (``ops.tune_fused`` / ``ops.tune_skinny_splits``) times every layout
@@ -7,6 +8,9 @@ launch is reported with the effective bandwidth over the weight bytes.
 
     python scripts/exp/fp8_gemm_bench.py --weights bf16 --out bf16.jsonl
     python scripts/exp/fp8_gemm_bench.py --weights fp8 --out fp8.jsonl
+    python scripts/exp/fp8_gemm_bench.py --weights mxfp4 --out mxfp4.jsonl
+
+``--weights mxfp4`` has no lm_head row: the head stays on the fp8 stream.
 
 ``--weights bf16`` uses nothing that the fp8 path added, so it also runs on a
 tree without it (the baseline figures).
@@ -41,13 +45,14 @@ SHAPES = [
 
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__)
-    ap.add_argument("--weights", choices=["bf16", "fp8"], default="bf16")
+    ap.add_argument("--weights", choices=["bf16", "fp8", "mxfp4"], default="bf16")
     ap.add_argument("--mpads", type=int, nargs="+", default=[16, 64])
     ap.add_argument("--models", nargs="+", default=["8b", "70b"])
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     dev = torch.device("cuda")
-    fp8 = args.weights == "fp8"
+    fp8, mx4 = args.weights == "fp8", args.weights == "mxfp4"
+    tag = (args.weights,) if fp8 or mx4 else ()
     timed: list = []
     real = ops.graph_time
 
@@ -58,12 +63,13 @@ def main() -> int:
     ops.graph_time = recording
     rows = []
     for model, name, mode, N, K, norm, heads in SHAPES:
-        if model not in args.models:
+        if model not in args.models or (mx4 and mode == "head"):
             continue
         w = torch.randn(N, K, device=dev, dtype=torch.bfloat16) * 0.02
-        wp = ops.quantize_weight_fp8(w) if fp8 else ops.shuffle_weight(w)
+        wp = ops.quantize_weight_mxfp4(w) if mx4 else ops.quantize_weight_fp8(w) if fp8 \
+            else ops.shuffle_weight(w)
         del w
-        wbytes = N * K * (1 if fp8 else 2)
+        wbytes = N * K * 17 // 32 if mx4 else N * K * (1 if fp8 else 2)
         cs = ref.rope_cos_sin(heads[2], 4096, 500000.0, device=dev) if heads else None
         for Mpad in args.mpads:
             timed.clear()
@@ -73,7 +79,7 @@ def main() -> int:
             else:
                 ops.tune_fused(wp, mode, mpads=(Mpad,), norm=norm, heads=heads, cos_sin=cs)
                 layout = [v for k, v in ops._FSPLITS.items()
-                          if k[:4] == (mode, N, K, Mpad) and (len(k) > 4) == fp8]
+                          if k[:4] == (mode, N, K, Mpad) and tuple(k[4:]) == tag]
             us = min(timed)
             row = dict(weights=args.weights, model=model, gemm=name, N=N, K=K, Mpad=Mpad,
                        layout=layout, us=round(us, 2), weight_bytes=wbytes,

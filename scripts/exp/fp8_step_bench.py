@@ -1,8 +1,9 @@
 """One whole Llama decode step (fused decode GEMMs, graph replay) and the
-resident weight bytes, bf16 against the fp8 (e4m3) weight stream.
+resident weight bytes, bf16 against the fp8 (e4m3) and MXFP4 weight streams.
 
     python scripts/exp/fp8_step_bench.py --weights bf16 [--model llama3-8b]
     python scripts/exp/fp8_step_bench.py --weights fp8
+    python scripts/exp/fp8_step_bench.py --weights mxfp4
 
 ``--seqs`` sequences each feed one token per step (8 -> Mpad 16) on a context
 of ``--ctx`` tokens. ``--weights bf16`` uses nothing that the fp8 path added, so
@@ -37,6 +38,8 @@ def resident_bytes(w) -> int:
                 total += t.untyped_storage().nbytes()
         elif hasattr(t, "wp") and hasattr(t, "scale"):
             add(t.wp); add(t.scale)
+        elif hasattr(t, "wp") and hasattr(t, "scales"):
+            add(t.wp); add(t.scales)
     for t in (w.embed, getattr(w, "lm_head", None), getattr(w, "lm_head_p", None), w.final_norm):
         add(t)
     for L in list(w.layers) + list(getattr(w, "decode_layers", [])):
@@ -47,13 +50,13 @@ def resident_bytes(w) -> int:
 
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__)
-    ap.add_argument("--weights", choices=["bf16", "fp8"], default="bf16")
+    ap.add_argument("--weights", choices=["bf16", "fp8", "mxfp4"], default="bf16")
     ap.add_argument("--model", default="llama3-8b")
     ap.add_argument("--seqs", type=int, default=8)
     ap.add_argument("--ctx", type=int, default=64)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    kw = dict(weight_dtype="fp8") if args.weights == "fp8" else {}
+    kw = dict(weight_dtype=args.weights) if args.weights != "bf16" else {}
     eng = LLMEngine(llama_config(args.model), "cuda", max_seqs=args.seqs, max_seq_len=1024,
                     use_graphs=False, compact=True, **kw)
     Mpad = ops.mpad_for(args.seqs)

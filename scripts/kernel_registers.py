@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Registers, occupancy and LDS of the hot decode kernels, from the compiler's
 resource remarks (``hipcc -Rpass-analysis=kernel-resource-usage``, device-only
-compile of ``gemm_skinny.hip``, ``gemm_skinny_fp8.hip`` and ``attn_decode.hip`` for gfx950; ~2 min).
+compile of ``gemm_skinny.hip``, ``gemm_skinny_fp8.hip``, ``gemm_skinny_mxfp4.hip`` and
+``attn_decode.hip`` for gfx950; ~3 min).
 
 The question it answers: can a Whisper decoder wave sit beside an LLM decode
 GEMM workgroup on the same CU (one 512-entry VGPR + AGPR file per SIMD lane)?
@@ -34,6 +35,10 @@ LABELS = {
     "SF8<2, 1, 4, 1, 2, 0, 0>": "8B down, fp8 weight stream",
     "SF8<2, 1, 4, 1, 3, 1, 0>": "8B qkv, fp8 weight stream",
     "SF8<1, 1, 4, 1, 2, 0, 0>": "8B o, fp8 weight stream",
+    "SF4<2, 1, 4, 4, 1, 1, 0>": "8B gate|up, MXFP4 weight stream",
+    "SF4<2, 1, 4, 1, 2, 0, 0>": "8B down, MXFP4 weight stream",
+    "SF4<2, 1, 4, 1, 3, 1, 0>": "8B qkv, MXFP4 weight stream",
+    "SF4<1, 1, 4, 1, 2, 0, 0>": "8B o, MXFP4 weight stream",
     "attn_decode_kernel<128, 0, 4, 2>": "Llama decode attention (D 128)",
     "attn_decode_kernel<64, 0, 4, 2>": "Whisper self / cross attention (D 64)",
 }
@@ -58,13 +63,14 @@ def main() -> int:
           "-Rpass-analysis=kernel-resource-usage; scripts/kernel_registers.py)")
     print("# V = arch VGPRs, A = AGPRs (one 512-entry file per SIMD lane); occ = waves per SIMD "
           "of the kernel alone")
-    for src in ("gemm_skinny.hip", "gemm_skinny_fp8.hip", "attn_decode.hip"):
+    for src in ("gemm_skinny.hip", "gemm_skinny_fp8.hip", "gemm_skinny_mxfp4.hip", "attn_decode.hip"):
         blocks = re.split(r"remark: Function Name: ", remarks(src))[1:]
         names = [b.split(" ")[0] for b in blocks]
         dem = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True,
                              text=True).stdout.split("\n")
         for b, d in zip(blocks, dem):
-            d = (d.replace("skinny_fused_fp8_kernel", "SF8").replace("skinny_fused_kernel", "SF")
+            d = (d.replace("skinny_fused_fp8_kernel", "SF8").replace("skinny_fused_mxfp4_kernel", "SF4")
+                 .replace("skinny_fused_kernel", "SF")
                  .replace("(FusedArgs)", "")
                  .replace("(AttnDecArgs)", "").replace("void ", "").strip())
             if d in LABELS:
