@@ -364,12 +364,7 @@ def pcm16_to_f32_padded(pcm: torch.Tensor, offsets: torch.Tensor, ld: int,
     per-segment sum of squares [S] of the kept samples."""
     S = offsets.numel() - 1
     if not _gpu(pcm):
-        out = torch.zeros(S, ld, dtype=torch.float32)
-        seg = offsets.cpu()
-        for i in range(S):
-            n = min(int(seg[i + 1] - seg[i]), ld)
-            out[i, :n] = pcm[int(seg[i]):int(seg[i]) + n].float() / 32767.0
-        return out, out.square().sum(1)
+        return ref.pcm16_to_f32_padded(pcm, offsets, ld)
     assert pcm.dtype == torch.int16 and pcm.is_contiguous()
     assert offsets.dtype == torch.int64 and offsets.is_contiguous() and offsets.is_cuda
     out = torch.empty(S, ld, dtype=torch.float32, device=pcm.device)
@@ -964,8 +959,9 @@ def embed_pos(tokens: torch.Tensor, positions: torch.Tensor, tok_embed: torch.Te
     """bf16(tok_embed[tokens] + pos_embed[positions]) [rows, d]."""
     rows, d = tokens.numel(), tok_embed.shape[1]
     if not _gpu(tok_embed):
-        return (tok_embed[tokens.long()].float() + pos_embed[positions.long()].float()).to(
-            torch.bfloat16)
+        # a negative id (a padding row) reads row 0, as the kernel does
+        return (tok_embed[tokens.long().clamp(min=0)].float()
+                + pos_embed[positions.long()].float()).to(torch.bfloat16)
     assert tokens.dtype == torch.int32 and positions.dtype == torch.int32
     out = out if out is not None else torch.empty(rows, d, dtype=torch.bfloat16,
                                                   device=tok_embed.device)
@@ -983,7 +979,7 @@ def embed_stats(tokens: torch.Tensor, tok_embed: torch.Tensor, scratch: "FusedSc
     layer 0's norm prologue (what ``scratch.seed_stats`` computes)."""
     rows, d = tokens.numel(), tok_embed.shape[1]
     if not _gpu(tok_embed):
-        x = tok_embed[tokens.long()]
+        x = tok_embed[tokens.long().clamp(min=0)]
         if pos_embed is not None:
             x = (x.float() + pos_embed[positions.long()].float()).to(torch.bfloat16)
         scratch.seed_stats(x, sums=sums)

@@ -195,12 +195,31 @@ def pack_mask(bits: torch.Tensor) -> torch.Tensor:
     return w.to(torch.int32)
 
 
+def _pcm16_to_f32(pcm):
+    """x / 32767 as the kernels compute it: one f32 multiply by the f32 nearest
+    to 1 / 32767 (within one f32 ulp of the quotient; ``pcm.float() / 32767``
+    differs from it in the last bit for 1536 of the 65536 values)."""
+    return pcm.float() * torch.tensor(1.0 / 32767.0, dtype=torch.float32)
+
+
 def pcm16_to_f32_sumsq(pcm, offsets):
-    f = pcm.float() / 32767.0
+    f = _pcm16_to_f32(pcm)
     off = offsets.tolist()
     ss = torch.tensor([float((f[off[i]:off[i + 1]].double() ** 2).sum()) for i in range(len(off) - 1)],
                       dtype=torch.float32)
     return f, ss
+
+
+def pcm16_to_f32_padded(pcm, offsets, ld):
+    """Segment s in row s of out [S, ld] (truncated to ``ld`` samples, +0.0
+    beyond it) and the sum of squares of the kept samples."""
+    off = offsets.tolist()
+    S = len(off) - 1
+    out = torch.zeros(S, ld, dtype=torch.float32)
+    for i in range(S):
+        n = min(off[i + 1] - off[i], ld)
+        out[i, :n] = _pcm16_to_f32(pcm[off[i]:off[i] + n])
+    return out, out.double().square().sum(1).float()
 
 
 # ------------------------------------------------------------- log-mel consts
