@@ -19,6 +19,11 @@ import os
 import re
 from dataclasses import dataclass, field
 
+# PCM sample rates the hub converts between (csrc/kernels/resample.hip): what a
+# relay may record at (HUB_AUDIO_INPUT_RATE=relay) and a reply may be played at
+# (HUB_TTS_SAMPLE_RATE)
+AUDIO_SAMPLE_RATES = (8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000)
+
 _DUR_RE = re.compile(r"([0-9]*\.?[0-9]+)(ns|us|µs|ms|s|m|h)")
 _UNIT = {"ns": 1e-9, "us": 1e-6, "µs": 1e-6, "ms": 1e-3, "s": 1.0, "m": 60.0, "h": 3600.0}
 
@@ -210,6 +215,14 @@ class GPUConfig:
     # backend); below stt_confirm_below the hub asks the user to confirm
     stt_confidence: str = "heuristic"
     stt_confirm_below: float = 0.6
+    # relay audio: "fixed" (every chunk is 16 kHz, AudioChunk.sample_rate is
+    # ignored: the reference's behaviour) or "relay" (the stream's own rate, one
+    # of AUDIO_SAMPLE_RATES; the gpu STT resamples it to 16 kHz on the device,
+    # an external STT gets it in the WAV header)
+    audio_input_rate: str = "fixed"
+    # reply audio of the gpu voice: 0 = the voice's own rate (22.05 kHz random
+    # init, 16 kHz MMS), else one of AUDIO_SAMPLE_RATES (resampled on the device)
+    tts_sample_rate: int = 0
     tts_backend: str = "gpu"          # gpu | http | none
     use_graphs: bool = True
     seed: int = 0
@@ -329,6 +342,13 @@ class Config:
         if self.gpu.stt_confidence == "acoustic" and self.gpu.stt_backend != "gpu":
             raise ConfigError("HUB_STT_CONFIDENCE=acoustic needs HUB_STT_BACKEND=gpu: "
                               f"{self.gpu.stt_backend}")
+        if self.gpu.audio_input_rate not in ("fixed", "relay"):
+            raise ConfigError("invalid HUB_AUDIO_INPUT_RATE (fixed | relay): "
+                              f"{self.gpu.audio_input_rate}")
+        if self.gpu.tts_sample_rate != 0 and self.gpu.tts_sample_rate not in AUDIO_SAMPLE_RATES:
+            raise ConfigError("invalid HUB_TTS_SAMPLE_RATE (0 | "
+                              f"{' | '.join(map(str, AUDIO_SAMPLE_RATES))}): "
+                              f"{self.gpu.tts_sample_rate}")
         if not 0.0 <= self.gpu.stt_confirm_below <= 1.0:
             raise ConfigError("HUB_STT_CONFIRM_BELOW must be in [0, 1]: "
                               f"{self.gpu.stt_confirm_below}")
@@ -346,6 +366,16 @@ def parse_relay_groups(s: str) -> dict:
 
 class ConfigError(ValueError):
     pass
+
+
+def _tts_sample_rate(e) -> int:
+    """``HUB_TTS_SAMPLE_RATE``: an integer (not silently the default: a typo
+    would leave the relays playing the reply at the wrong speed)."""
+    v = env_str(e, "0", "HUB_TTS_SAMPLE_RATE").strip()
+    try:
+        return int(v)
+    except ValueError:
+        raise ConfigError(f"invalid configuration: invalid HUB_TTS_SAMPLE_RATE: {v}") from None
 
 
 def load(env=None) -> Config:
@@ -426,6 +456,8 @@ def load(env=None) -> Config:
             stt_backend=env_str(e, "gpu", "HUB_STT_BACKEND"),
             stt_confidence=env_str(e, "heuristic", "HUB_STT_CONFIDENCE").lower(),
             stt_confirm_below=env_float(e, 0.6, "HUB_STT_CONFIRM_BELOW"),
+            audio_input_rate=env_str(e, "fixed", "HUB_AUDIO_INPUT_RATE").lower(),
+            tts_sample_rate=_tts_sample_rate(e),
             tts_backend=env_str(e, "gpu", "HUB_TTS_BACKEND"),
             use_graphs=env_bool(e, True, "HUB_USE_GRAPHS"),
             seed=env_int(e, 0, "HUB_SEED"),

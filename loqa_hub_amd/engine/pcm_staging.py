@@ -24,7 +24,10 @@ the host and copied at upload - nothing is dropped below ``MAX_SAMPLES``
 the host: the reference's per-sample ``bytesToFloat32Array``
 (``audio_service.go:1048-1101``) and WAV/HTTP round trip
 (``stt_client.go:365-398``) have no counterpart here - the f32 conversion is
-the fused ``pcm16_f32_pad`` kernel on the device.
+the fused ``pcm16_f32_pad`` kernel on the device, and for a relay that does not
+record at 16 kHz (``HUB_AUDIO_INPUT_RATE=relay``) its resampling sibling
+``pcm16_resample_pad``: slots, chains, stream-in and the host tail hold source
+samples at the relay's rate.
 
 A slot is recycled only after its copy's event has completed (the stager
 checks the event on acquire), so a relay can never overwrite samples that are
@@ -48,15 +51,19 @@ log = logging.getLogger("loqa.pcm")
 FLUSH_SAMPLES = int(os.environ.get("LOQA_PCM_FLUSH_SAMPLES", "32768"))
 # longest utterance kept (the reference keeps everything; a bound here keeps
 # one runaway relay from exhausting host memory)
-MAX_SAMPLES = int(float(os.environ.get("HUB_MAX_UTTERANCE_S", "600")) * 16000)
+MAX_UTTERANCE_S = float(os.environ.get("HUB_MAX_UTTERANCE_S", "600"))
+MAX_SAMPLES = int(MAX_UTTERANCE_S * 16000)      # at 16 kHz
 
 
 class PCMSlot:
-    """One utterance's pinned sample buffer: a chain of stager slots (30 s
-    each) plus a host tail when the stager ran out of slots."""
+    """One utterance's pinned sample buffer: a chain of stager slots (480000
+    samples each: 30 s at 16 kHz, 10 s at 48 kHz) plus a host tail when the
+    stager ran out of slots. Everything here counts source samples, at the
+    relay's ``rate``; the STT upload resamples on the device."""
 
-    def __init__(self, stager: "PcmStager", slot: int, stream: bool = True):
+    def __init__(self, stager: "PcmStager", slot: int, stream: bool = True, rate: int = 16000):
         self.stager = stager
+        self.rate = rate
         self.stream = stream and stager.stream_in   # copy chunks as they arrive
         self.slots = [slot]
         self.host_tail = bytearray()
@@ -71,9 +78,10 @@ class PCMSlot:
         """Append PCM16-LE bytes (an odd trailing byte is dropped, as the
         reference does); returns the samples kept."""
         n = len(data) & ~1
-        room = 2 * (MAX_SAMPLES - self._n)
+        limit = self.max_samples
+        room = 2 * (limit - self._n)
         if n > room:
-            self.stager.note_overflow((n - max(room, 0)) // 2, MAX_SAMPLES)
+            self.stager.note_overflow((n - max(room, 0)) // 2, limit, self.rate)
             n = max(room, 0)
         if n <= 0:
             return 0
@@ -107,6 +115,11 @@ class PCMSlot:
 
     def __len__(self) -> int:
         return self._n
+
+    @property
+    def max_samples(self) -> int:
+        """``HUB_MAX_UTTERANCE_S`` in samples at the slot's rate."""
+        return MAX_SAMPLES if self.rate == 16000 else int(MAX_UTTERANCE_S * self.rate)
 
     def numpy(self) -> np.ndarray:
         """int16 samples: a zero-copy view of the pinned slot when the chain is
@@ -203,11 +216,11 @@ class PcmStager:
                 self.chained += 1
         return slot
 
-    def note_overflow(self, samples: int, limit: int) -> None:
+    def note_overflow(self, samples: int, limit: int, rate: int = 16000) -> None:
         self.overflows += 1
         self.overflow_samples += samples
         log.error("utterance longer than %.0f s: %d samples dropped (HUB_MAX_UTTERANCE_S)",
-                  limit / 16000, samples)
+                  limit / rate, samples)
 
     def host_copy(self, dst_ptr: int, pinned, wait_stream: int) -> None:
         """H2D copy of a pinned host tensor (a chain's host tail) ordered on

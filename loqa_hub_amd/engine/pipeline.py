@@ -42,6 +42,7 @@ class PipelineJob:
     transcript_hint: str | list | None = None
     staged: object = None                  # pinned PCM slot with the samples (relay path)
     on_tokens: object = None               # streaming hook: called with each step's token ids
+    sample_rate: int = 16000               # the rate ``pcm`` / ``staged`` were recorded at
     # results
     transcription: TranscriptionResult | None = None
     raw_text: str = ""
@@ -63,8 +64,9 @@ class PipelineJob:
 def _stt_request(j: PipelineJob) -> STTRequest:
     h = j.transcript_hint
     if isinstance(h, (list, tuple)):
-        return STTRequest(j.pcm, transcript=" ".join(h), transcript_windows=list(h), staged=j.staged)
-    return STTRequest(j.pcm, transcript=h, staged=j.staged)
+        return STTRequest(j.pcm, transcript=" ".join(h), transcript_windows=list(h), staged=j.staged,
+                          sample_rate=j.sample_rate)
+    return STTRequest(j.pcm, transcript=h, staged=j.staged, sample_rate=j.sample_rate)
 
 
 class VoicePipeline:

@@ -58,11 +58,14 @@ def n_windows(n_samples: int, cap: int = MAX_WINDOWS) -> int:
 
 @dataclass(eq=False)
 class STTRequest:
-    pcm: np.ndarray                   # int16 samples @ 16 kHz
+    pcm: np.ndarray                   # int16 samples at ``sample_rate``
     transcript: str | None = None     # teacher-forcing target (synthetic mode)
     max_new_tokens: int = 96          # per 30 s window
     staged: object = None             # pinned PCM slot (engine/pcm_staging.py) holding the samples
-    n_samples: int = 0                # samples uploaded (<= MAX_WINDOWS x 30 s)
+    n_samples: int = 0                # 16 kHz samples transcribed (<= MAX_WINDOWS x 30 s)
+    # the rate ``pcm`` / ``staged`` were recorded at (ops.RESAMPLE_RATES); other
+    # than 16 kHz: resampled on the device by the upload's convert launch
+    sample_rate: int = 16000
     # teacher-forcing targets per 30 s window of a long-form utterance (else
     # ``transcript`` is split over the windows by words)
     transcript_windows: list | None = None
@@ -234,10 +237,17 @@ class STTEngine:
         here), each slot goes to HBM with one hipMemcpyAsync on the stager's
         H2D stream, and this (compute) stream waits on the copies' events.
         ``device_pcm`` (already on the GPU, e.g. scattered by the DP router
-        over RCCL) holds the concatenated samples and skips the copies."""
+        over RCCL) holds the concatenated samples and skips the copies.
+
+        A request recorded at another rate (``STTRequest.sample_rate``) is
+        uploaded as it is and resampled to 16 kHz by the convert launch: when
+        any request of the batch is not 16 kHz the launch is
+        ``ops.pcm16_resample_padded`` (one for the whole batch, 16 kHz requests
+        pass through), otherwise ``ops.pcm16_to_f32_padded`` as ever. Windows,
+        ``n_samples`` and the dropped-sample count are in 16 kHz samples."""
         lens = []
         for r in reqs:
-            n = self._n_samples(r)
+            n = self._n_out(r)          # everything below counts 16 kHz samples
             w = n_windows(n, self.max_windows)
             if n > w * N_SAMPLES:
                 self.stats["long_form_dropped_samples"] = \
@@ -249,12 +259,21 @@ class STTEngine:
             r.windows = w
         for r, n in zip(reqs, lens):
             r.n_samples = n
+        rates = [r.sample_rate or 16000 for r in reqs]
+        resampled = any(sr != 16000 for sr in rates)
+        assert not (resampled and device_pcm is not None), "device_pcm is 16 kHz"
+        out_lens = lens
+        if resampled:
+            # source samples uploaded per request: its own for 16 kHz, else what
+            # the kept outputs' filter taps reach (all of them unless truncated)
+            lens = [n if sr == 16000 else min(self._n_samples(r), self._src_reach(n, sr))
+                    for r, n, sr in zip(reqs, out_lens, rates)]
         offs = np.zeros(len(reqs) + 1, np.int64)
         offs[1:] = np.cumsum(lens)
         # one padded 30 s encoder row per window: a request's windows are
         # consecutive slices of its samples, so the rows' offsets are the
         # cumulative row lengths
-        row_lens = [min(N_SAMPLES, n - w * N_SAMPLES) for r, n in zip(reqs, lens)
+        row_lens = [min(N_SAMPLES, n - w * N_SAMPLES) for r, n in zip(reqs, out_lens)
                     for w in range(r.windows)]
         row_offs = np.zeros(len(row_lens) + 1, np.int64)
         row_offs[1:] = np.cumsum(row_lens)
@@ -281,6 +300,13 @@ class STTEngine:
                 if r.staged is not None:
                     r.staged.release()
                     r.staged = None
+        if resampled:
+            # one launch for the whole batch: a row is a 30 s window of its
+            # utterance's 16 kHz signal (16 kHz utterances pass through)
+            rows = [(int(o), n_src, w * N_SAMPLES, min(N_SAMPLES, n - w * N_SAMPLES), sr)
+                    for r, o, n_src, n, sr in zip(reqs, offs[:-1], lens, out_lens, rates)
+                    for w in range(r.windows)]
+            return ops.pcm16_resample_padded(pcm, rows, N_SAMPLES)
         off_t = torch.from_numpy(row_offs)
         if self.is_gpu:
             off_t = off_t.pin_memory().to(self.device, non_blocking=True)
@@ -289,6 +315,18 @@ class STTEngine:
     @staticmethod
     def _n_samples(r: STTRequest) -> int:
         return len(r.staged) if r.staged is not None else len(r.pcm)
+
+    @classmethod
+    def _n_out(cls, r: STTRequest) -> int:
+        """16 kHz samples of the request: ceil(n_src * 16000 / rate)."""
+        n, sr = cls._n_samples(r), r.sample_rate or 16000
+        return n if sr == 16000 else ops.ref.resample_len(n, ops.ref.check_rate(sr), 16000)
+
+    @staticmethod
+    def _src_reach(n_out: int, rate: int) -> int:
+        """Source samples the first ``n_out`` 16 kHz outputs read."""
+        _, L, M, T = ops.ref.resample_filter(rate, 16000)
+        return 0 if n_out <= 0 else (n_out - 1) * M // L + (T - 1) // 2 + 1
 
     @staticmethod
     def _host_samples(r: STTRequest) -> np.ndarray:
@@ -644,7 +682,7 @@ class STTEngine:
 
     def rows_needed(self, reqs: list[STTRequest]) -> int:
         """Encoder rows / cross-attention slots of ``reqs`` (one per 30 s window)."""
-        return sum(n_windows(self._n_samples(r), self.max_windows) for r in reqs)
+        return sum(n_windows(self._n_out(r), self.max_windows) for r in reqs)
 
     @property
     def max_windows(self) -> int:

@@ -28,6 +28,7 @@ import time
 import numpy as np
 import torch
 
+from .. import ops
 from ..llm.tts import TTSOptions, TTSResult
 from ..models.configs import VitsConfig
 from ..models.vits import VitsGraphRunner, VitsModel, VitsWeights, text_to_ids
@@ -53,12 +54,16 @@ def pcm16_to_wav(pcm: np.ndarray, sample_rate: int) -> bytes:
 class VitsTTSEngine:
     def __init__(self, cfg: VitsConfig | None, device, *, seed: int = 0, batch_window: float = 0.003,
                  max_batch: int = 32, use_graphs: bool = True, checkpoint: str | None = None,
-                 format_policy: str = "wav"):
+                 format_policy: str = "wav", sample_rate: int = 0):
         """``checkpoint``: a Hugging Face VITS / MMS-TTS directory (config.json,
         safetensors, vocab.json; models/loader.py ``load_vits``) — its config
         and vocabulary replace ``cfg`` and the character table; None: the
         random-init voice of ``cfg``. ``format_policy``: what an unsupported
-        response_format gets - "wav" (a logged, counted downgrade) or "error"."""
+        response_format gets - "wav" (a logged, counted downgrade) or "error".
+        ``sample_rate``: the rate of the returned audio (``HUB_TTS_SAMPLE_RATE``);
+        0 or the voice's own rate: the voice's PCM as it is, else that PCM
+        resampled on the device (``ops.pcm16_resample``) before it is copied
+        to the host."""
         if format_policy not in ("wav", "error"):
             raise ValueError(f"format_policy must be 'wav' or 'error', not {format_policy!r}")
         self.format_policy = format_policy
@@ -71,6 +76,11 @@ class VitsTTSEngine:
         else:
             weights = VitsWeights(cfg, self.device, seed=seed)
         self.cfg = cfg
+        if sample_rate:
+            ops.ref.check_rate(sample_rate)
+            ops.ref.check_rate(cfg.sample_rate)     # the voice's rate has a filter too
+        # the rate of everything this engine returns (WAV header, TTSResult)
+        self.sample_rate = sample_rate or cfg.sample_rate
         self.model = VitsModel(weights)
         # bucketed HIP-graph replay (models/vits.py VitsGraphRunner), built
         # lazily on the placed TTS stream
@@ -129,6 +139,10 @@ class VitsTTSEngine:
                 spk = torch.tensor(speakers or [0] * len(texts), dtype=torch.int64, device=self.device)
             pcm, n = synth(torch.from_numpy(arr).to(self.device), lens, seed=self._seed,
                            length_scale=ls, speakers=spk)
+            if self.sample_rate != self.cfg.sample_rate:
+                # one more launch on the TTS stream; the lengths stay on the device
+                pcm, n = ops.pcm16_resample(pcm, n.contiguous(), self.cfg.sample_rate,
+                                            self.sample_rate)
             t1 = time.perf_counter()
             pcm, n = pcm.cpu().numpy(), n.cpu().numpy()
             t2 = time.perf_counter()
@@ -212,8 +226,8 @@ class VitsTTSEngine:
         if fmt == "pcm":
             data = pcm.astype("<i2").tobytes()
         else:
-            data = pcm16_to_wav(pcm, self.cfg.sample_rate)
-        return TTSResult(data, _CONTENT_TYPES[fmt], len(data), self.cfg.sample_rate, format=fmt)
+            data = pcm16_to_wav(pcm, self.sample_rate)
+        return TTSResult(data, _CONTENT_TYPES[fmt], len(data), self.sample_rate, format=fmt)
 
     async def _flush(self) -> None:
         await asyncio.sleep(self.batch_window)

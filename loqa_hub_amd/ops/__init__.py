@@ -376,6 +376,92 @@ def pcm16_to_f32_padded(pcm: torch.Tensor, offsets: torch.Tensor, ld: int,
     return out, sumsq[:S]
 
 
+# sample-rate conversion (csrc/kernels/resample.hip): the rates a relay may
+# record at / a reply may be played at
+RESAMPLE_RATES = ref.RESAMPLE_RATES
+_resample_tables: dict = {}
+
+
+def resample_filter(rate_in: int, rate_out: int, device="cpu") -> tuple[torch.Tensor, int, int, int]:
+    """(f32 table [L, T] on ``device``, L, M, T) of the polyphase filter of
+    ``rate_in`` -> ``rate_out``: ``ref.resample_filter``'s fp64 table rounded
+    once to f32, kept per (pair, device). An unsupported rate: ValueError."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (rate_in, rate_out, device)
+    hit = _resample_tables.get(key)
+    if hit is None:
+        tab, L, M, T = ref.resample_filter(rate_in, rate_out)
+        import numpy as np
+        hit = _resample_tables[key] = (torch.from_numpy(tab.astype(np.float32)).to(device), L, M, T)
+    return hit
+
+
+def pcm16_resample_padded(pcm: torch.Tensor, rows, ld: int, rate_out: int = 16000
+                          ) -> tuple[torch.Tensor, torch.Tensor]:
+    """The resampling sibling of :func:`pcm16_to_f32_padded`, one launch for
+    rows of any supported rates. pcm: int16 [N] (concatenated utterances);
+    ``rows``: one host tuple (src_first, src_len, out_first, out_len, rate_in)
+    per output row - the utterance pcm[src_first : src_first + src_len] at
+    ``rate_in`` and the row's slice [out_first, out_first + out_len) of its
+    signal resampled to ``rate_out`` (a 30 s window: the filter reads across
+    the window boundary, so cutting an utterance into rows equals resampling it
+    whole). Returns (f32 [R, ld] = samples / 32767, +0.0 beyond out_len; sum of
+    squares [R]). A row already at ``rate_out`` is ``pcm16_to_f32_padded``'s bits."""
+    rows = [tuple(int(v) for v in r) for r in rows]
+    for r in rows:          # before any launch
+        ref.check_rate(r[4])
+        n_all = ref.resample_len(r[1], r[4], rate_out)
+        if min(r[:4]) < 0 or r[0] + r[1] > pcm.numel() or (r[3] and r[2] + r[3] > n_all):
+            raise ValueError(f"resample row {r} outside its utterance ({pcm.numel()} samples, "
+                             f"{n_all} outputs)")
+    if not _gpu(pcm):
+        return ref.pcm16_resample_padded(pcm, rows, ld, rate_out)
+    import numpy as np
+    assert pcm.dtype == torch.int16 and pcm.is_contiguous()
+    R = len(rows)
+    out = torch.empty(R, ld, dtype=torch.float32, device=pcm.device)
+    sumsq = torch.empty(max(R, 1), dtype=torch.float32, device=pcm.device)
+    if R == 0:
+        return out, sumsq[:0]
+    desc = np.zeros((R, 8), np.int64)
+    for i, r in enumerate(rows):
+        tab, L, M, T = resample_filter(r[4], rate_out, pcm.device)
+        desc[i] = (*r[:4], L, M, T, tab.data_ptr())
+    dev = torch.from_numpy(desc).pin_memory().to(pcm.device, non_blocking=True)
+    check(kernels().loqa_pcm16_resample_pad(ptr(pcm), ptr(out), ptr(dev), desc.ctypes.data,
+                                            ptr(sumsq), R, ld, stream_ptr(pcm)),
+          "pcm16_resample_pad")
+    return out, sumsq[:R]
+
+
+def pcm16_resample(pcm: torch.Tensor, lens: torch.Tensor, rate_in: int, rate_out: int
+                   ) -> tuple[torch.Tensor, torch.Tensor]:
+    """PCM16 rows [B, N] holding ``lens`` [B] samples (int32 / int64, on the
+    device: the host never reads them) at ``rate_in`` -> (int16 [B, ceil(N L /
+    M)] at ``rate_out``, zero beyond each row's length; int32 lengths [B],
+    ceil(len L / M), written by the kernel). Values: the f32 filter sum rounded
+    to nearest even, saturated to int16."""
+    ref.check_rate(rate_in), ref.check_rate(rate_out)
+    assert pcm.dim() == 2 and lens.numel() == pcm.shape[0]
+    if not _gpu(pcm):
+        return ref.pcm16_resample(pcm, lens, rate_in, rate_out)
+    B, N = pcm.shape
+    ld_in = pcm.stride(0) if B > 1 else N       # a single row's stride means nothing
+    assert pcm.dtype == torch.int16 and (N <= 1 or pcm.stride(1) == 1) and ld_in >= N
+    assert lens.dtype in (torch.int32, torch.int64) and lens.is_contiguous() and lens.is_cuda
+    tab, L, M, T = resample_filter(rate_in, rate_out, pcm.device)
+    ld_out = max(1, -(-N * L // M))
+    out = torch.empty(B, ld_out, dtype=torch.int16, device=pcm.device)
+    n_out = torch.empty(B, dtype=torch.int32, device=pcm.device)
+    check(kernels().loqa_pcm16_resample(ptr(pcm), ld_in, N, ptr(lens),
+                                        int(lens.dtype == torch.int64), ptr(out), ld_out,
+                                        ptr(n_out), B, L, M, T, ptr(tab), stream_ptr(pcm)),
+          "pcm16_resample")
+    return out, n_out
+
+
 def log_mel(audio: torch.Tensor, consts: "ref.MelConstants") -> torch.Tensor:
     """audio [B, n_samples] f32 (padded to 30 s) -> whisper log-mel [B, n_mels, frames] bf16."""
     if not _gpu(audio):

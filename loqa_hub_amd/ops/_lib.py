@@ -91,6 +91,12 @@ _KERNEL_SIGS = {
                             c_int, c_int, c_int, c_int, c_int, c_void_p],
     "loqa_pcm16_f32_sumsq": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_ll, c_void_p],
     "loqa_pcm16_f32_pad": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_ll, c_void_p],
+    # (pcm, out, rows, rows_host, sumsq, nrows, ld, stream)
+    "loqa_pcm16_resample_pad": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_ll,
+                                c_void_p],
+    # (in, ld_in, max_in, n, n_is64, out, ld_out, n_out, B, L, M, T, table, stream)
+    "loqa_pcm16_resample": [c_void_p, c_ll, c_ll, c_void_p, c_int, c_void_p, c_ll, c_void_p, c_int, c_int,
+                            c_int, c_int, c_void_p, c_void_p],
     "loqa_masked_argmax": [c_void_p, c_int, c_ll, c_int, c_int, c_void_p, c_void_p, c_int,
                            # (..., out_idx, workspace, token_ids, stream)
                            c_void_p, c_void_p, c_void_p, c_void_p],

@@ -5,11 +5,14 @@ against them) and the CPU execution path (no GPU in the CI tier).
 """
 from __future__ import annotations
 
+import functools
 import math
 from dataclasses import dataclass
 
 import numpy as np
 import torch
+
+from ..config import AUDIO_SAMPLE_RATES as RESAMPLE_RATES
 
 
 def rmsnorm(x, w, eps, residual=None):
@@ -220,6 +223,116 @@ def pcm16_to_f32_padded(pcm, offsets, ld):
         n = min(off[i + 1] - off[i], ld)
         out[i, :n] = _pcm16_to_f32(pcm[off[i]:off[i] + n])
     return out, out.double().square().sum(1).float()
+
+
+# ------------------------------------------------------ sample-rate conversion
+# One filter definition for the kernel (csrc/kernels/resample.hip) and this
+# reference: a Kaiser-windowed sinc, evaluated per output phase.
+RESAMPLE_CUTOFF = 0.945     # of the lower Nyquist
+RESAMPLE_ZEROS = 32         # sinc zero crossings per side
+RESAMPLE_BETA = 12.0
+
+
+def check_rate(rate) -> int:
+    if rate not in RESAMPLE_RATES:
+        raise ValueError(f"unsupported sample rate {rate}")
+    return int(rate)
+
+
+@functools.lru_cache(maxsize=None)
+def resample_filter(rate_in: int, rate_out: int):
+    """(table fp64 [L, T], L, M, T) of ``rate_in`` -> ``rate_out``: output n
+    sits at source time n * M / L, base = n * M // L, phase = n * M % L and
+    y[n] = sum_j x[base - H + j] * table[phase, j], H = (T - 1) // 2, where
+    table[p, j] = h(p / L - (j - H)), h(tau) = c sinc(c tau) kaiser(tau / W; 12)
+    for |tau| < W, c = 0.945 min(1, rate_out / rate_in), W = 32 / c. No
+    per-phase renormalisation. The table is read-only (cached per pair)."""
+    rate_in, rate_out = check_rate(rate_in), check_rate(rate_out)
+    if rate_in == rate_out:                 # nothing to convert: the identity, one tap
+        tab = np.ones((1, 1), np.float64)
+        tab.setflags(write=False)
+        return tab, 1, 1, 1
+    g = math.gcd(rate_in, rate_out)
+    L, M = rate_out // g, rate_in // g
+    c = RESAMPLE_CUTOFF * min(1.0, rate_out / rate_in)
+    W = RESAMPLE_ZEROS / c
+    H = int(math.ceil(W))
+    T = 2 * H + 1
+    tau = np.arange(L, dtype=np.float64)[:, None] / L - (np.arange(T, dtype=np.float64)[None] - H)
+    a2 = np.clip(1.0 - (tau / W) ** 2, 0.0, None)
+    tab = c * np.sinc(c * tau) * np.i0(RESAMPLE_BETA * np.sqrt(a2)) / np.i0(RESAMPLE_BETA)
+    tab[np.abs(tau) >= W] = 0.0
+    tab.setflags(write=False)
+    return tab, L, M, T
+
+
+def resample_len(src_len: int, rate_in: int, rate_out: int) -> int:
+    """Output samples of ``src_len`` source samples: ceil(src_len * L / M)."""
+    _, L, M, _ = resample_filter(rate_in, rate_out)
+    return -(-int(src_len) * L // M)
+
+
+def resample(x, rate_in: int, rate_out: int, first: int = 0, count: int | None = None,
+             table=None) -> np.ndarray:
+    """fp64 resample of the 1-D signal ``x`` (zeros outside it): outputs
+    [first, first + count) of its resample_len(len(x)) samples (default: all).
+    ``table``: another [L, T] table of the pair (the kernel's f32-rounded one)."""
+    tab, L, M, T = resample_filter(rate_in, rate_out)
+    if table is not None:
+        tab = np.asarray(table, np.float64)
+    x = np.asarray(x.numpy() if isinstance(x, torch.Tensor) else x)
+    n_all = -(-x.shape[0] * L // M)
+    count = n_all - first if count is None else count
+    assert first >= 0 and count >= 0 and first + count <= n_all
+    out = np.zeros(count, np.float64)
+    H = (T - 1) // 2
+    step = max(1, (1 << 22) // T)                # bounds the gathered [step, T] block
+    for o in range(0, count, step):
+        t = (first + o + np.arange(min(step, count - o), dtype=np.int64)) * M
+        base, phase = t // L, t % L
+        lo, hi = int(base[0]) - H, int(base[-1]) + H + 1
+        seg = np.zeros(hi - lo, np.float64)
+        a, b = max(lo, 0), min(hi, x.shape[0])
+        if b > a:
+            seg[a - lo:b - lo] = x[a:b]
+        idx = (base - base[0])[:, None] + np.arange(T)[None]
+        out[o:o + t.shape[0]] = np.einsum("nt,nt->n", seg[idx], tab[phase])
+    return out
+
+
+def pcm16_resample_padded(pcm, rows, ld, rate_out: int = 16000):
+    """The resampling sibling of ``pcm16_to_f32_padded``. ``rows``: one
+    (src_first, src_len, out_first, out_len, rate_in) per output row - the
+    utterance's samples pcm[src_first : src_first + src_len] at ``rate_in``,
+    and the row's slice [out_first, out_first + out_len) of the utterance's
+    resampled signal (a 30 s window of it). Returns (f32 [R, ld]: the slice
+    * f32(1 / 32767), +0.0 beyond it; the rows' sums of squares [R])."""
+    rows = [tuple(int(v) for v in r) for r in rows]
+    scale = float(np.float32(1.0 / 32767.0))
+    x = pcm.numpy() if isinstance(pcm, torch.Tensor) else np.asarray(pcm)
+    out = torch.zeros(len(rows), ld, dtype=torch.float32)
+    for i, (s0, sn, o0, on, rate) in enumerate(rows):
+        check_rate(rate)
+        on = max(0, min(on, ld))
+        if on:
+            y = resample(x[s0:s0 + sn].astype(np.float64), rate, rate_out, o0, on)
+            out[i, :on] = torch.from_numpy((y * scale).astype(np.float32))
+    return out, out.double().square().sum(1).float()
+
+
+def pcm16_resample(pcm, lens, rate_in: int, rate_out: int):
+    """int16 [B, N] with lengths [B] -> (int16 [B, resample_len(N)], int32
+    lengths [B]): the fp64 resample rounded to nearest even and saturated."""
+    _, L, M, _ = resample_filter(rate_in, rate_out)
+    x = pcm.numpy() if isinstance(pcm, torch.Tensor) else np.asarray(pcm)
+    n = np.clip(np.asarray(lens.cpu() if isinstance(lens, torch.Tensor) else lens, np.int64),
+                0, x.shape[1])
+    n_out = -(-n * L // M)
+    out = np.zeros((x.shape[0], max(1, -(-x.shape[1] * L // M))), np.int16)
+    for b in range(x.shape[0]):
+        y = resample(x[b, :n[b]].astype(np.float64), rate_in, rate_out)
+        out[b, :n_out[b]] = np.clip(np.rint(y), -32768, 32767).astype(np.int16)
+    return torch.from_numpy(out), torch.from_numpy(n_out.astype(np.int32))
 
 
 # ------------------------------------------------------------- log-mel consts

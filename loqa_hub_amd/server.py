@@ -58,7 +58,8 @@ def build_tts(cfg: Config, device: str = "cuda:0"):
         ckpt = cfg.gpu.tts_checkpoint or None
         return VitsTTSEngine(None if ckpt else vits_config(cfg.gpu.tts_model), device,
                              seed=cfg.gpu.seed, batch_window=win, checkpoint=ckpt,
-                             format_policy=cfg.gpu.tts_format_policy)
+                             format_policy=cfg.gpu.tts_format_policy,
+                             sample_rate=cfg.gpu.tts_sample_rate)
     if b in ("http", "openai"):
         from .llm.tts import OpenAITTSClient
         return OpenAITTSClient(cfg.tts)
@@ -265,7 +266,7 @@ class HubServer:
             single_relay_bypass=a.single_relay_bypass,
             end_of_speech_wait=a.end_of_speech_wait, events_store=self.events,
             audio_publisher=publisher, confirmation_enabled=a.confirmation_enabled,
-            transcript_hints=self.transcript_hints)
+            transcript_hints=self.transcript_hints, input_rate=self.cfg.gpu.audio_input_rate)
         host = host if host is not None else self.cfg.server.host
         self.grpc_server = grpc.aio.server()
         add_audio_service(self.grpc_server, self.audio_service)

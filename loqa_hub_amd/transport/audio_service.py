@@ -32,6 +32,7 @@ from typing import Protocol
 
 import numpy as np
 
+from ..config import AUDIO_SAMPLE_RATES
 from ..events import VoiceEvent
 from ..utils import logging as hublog
 from .audio_proto import AudioResponse
@@ -72,6 +73,10 @@ class RelayStream:
     pcm: bytearray = field(default_factory=bytearray)
     pcm_slot: object = None
     n_samples: int = 0
+    # HUB_AUDIO_INPUT_RATE=relay: the stream's rate, its first non-zero
+    # AudioChunk.sample_rate (0: none seen, 16 kHz); later changes are ignored
+    sample_rate: int = 0
+    rate_change_logged: bool = False
 
     def add_pcm(self, data: bytes) -> None:
         data = data[: len(data) & ~1]
@@ -163,7 +168,13 @@ class AudioService:
                  scope: str = "global", relay_groups: dict[str, str] | None = None,
                  end_of_speech_wait: float = 5.0, result_timeout: float = 30.0,
                  events_store=None, audio_publisher=None, confirmation_enabled: bool = False,
-                 transcript_hints=None, single_relay_bypass: bool = False):
+                 transcript_hints=None, single_relay_bypass: bool = False,
+                 input_rate: str = "fixed"):
+        if input_rate not in ("fixed", "relay"):
+            raise ValueError(f"input_rate must be 'fixed' or 'relay', not {input_rate!r}")
+        # "fixed": every sample is 16 kHz whatever the chunks say (the
+        # reference, audio_service.go:609); "relay": the stream's own rate
+        self.input_rate = input_rate
         self.processor = processor
         self.arbitration_window_duration = window_duration
         self.scope = scope
@@ -186,7 +197,7 @@ class AudioService:
         self.windows: dict[str, ArbitrationWindow] = {}
         self.active_streams: dict[str, RelayStream] = {}
         self.stats = {"windows": 0, "arbitrations": 0, "cancelled": 0, "processed": 0, "late": 0,
-                      "bypassed": 0}
+                      "bypassed": 0, "rate_changes": 0, "unsupported_rate": 0}
 
     # ------------------------------------------------------------ windows
     def window_key(self, relay_id: str) -> str:
@@ -330,7 +341,8 @@ class AudioService:
             pass
         request_id = rs.request_id or f"req_{time.time_ns()}"
         ev = VoiceEvent.new(rs.relay_id, request_id)
-        ev.set_audio_metadata(rs.n_samples, 16000, True)
+        rate = (rs.sample_rate or 16000) if self.input_rate == "relay" else 16000
+        ev.set_audio_metadata(rs.n_samples, rate, True)
         if rs.n_samples == 0:
             rs.release_pcm()
             hublog.log_warn("winner has no audio", relay_id=rs.relay_id)
@@ -339,6 +351,12 @@ class AudioService:
             rs.release_pcm()
             res = UtteranceResult(success=False, command="error", response_text=MSG_STT_FAILED,
                                   error="no voice processor configured")
+        elif rate not in AUDIO_SAMPLE_RATES:
+            rs.release_pcm()
+            self.stats["unsupported_rate"] += 1
+            hublog.log_warn("unsupported sample rate", relay_id=rs.relay_id, sample_rate=rate)
+            res = UtteranceResult(success=False, command="error", response_text=MSG_STT_FAILED,
+                                  error=f"unsupported sample rate {rate}")
         else:
             kw = {}
             if getattr(self.processor, "takes_pcm16", False):
@@ -355,7 +373,7 @@ class AudioService:
             if hint:
                 kw["transcript_hint"] = hint
             try:
-                res = await self.processor.process(rs.relay_id, request_id, audio, 16000, **kw)
+                res = await self.processor.process(rs.relay_id, request_id, audio, rate, **kw)
             except Exception as e:  # processor failure -> spoken error
                 log.exception("voice processing failed for relay %s", rs.relay_id)
                 res = UtteranceResult(success=False, command="error", response_text=MSG_STT_FAILED,
@@ -432,12 +450,14 @@ class AudioService:
                     rs = self.active_streams.get(relay_id)
                     if rs is not None:
                         self._attach_pcm(rs)
+                        self._note_rate(rs, chunk)
                         rs.wake_pcm += data[: len(data) & ~1]
                         rs.add_pcm(data)
                         rs.request_id = request_id
                 else:
                     rs = self.active_streams.get(relay_id)
                     if rs is not None and rs.status != RelayStatus.CANCELLED:
+                        self._note_rate(rs, chunk)
                         rs.add_pcm(data)
                 if chunk.is_end_of_speech:
                     hublog.log_audio_processing(relay_id, "end_of_speech_detected")
@@ -461,6 +481,24 @@ class AudioService:
             new_slot = getattr(self.processor, "new_pcm_slot", None)
             if new_slot is not None:
                 rs.pcm_slot = new_slot()
+
+    def _note_rate(self, rs: RelayStream, chunk) -> None:
+        """``relay`` mode: the stream's rate is its first non-zero
+        ``chunk.sample_rate``; a later, different one is counted and logged
+        once per stream, and the first stands."""
+        rate = int(getattr(chunk, "sample_rate", 0) or 0)
+        if self.input_rate != "relay" or rate == 0 or rate == rs.sample_rate:
+            return
+        if rs.sample_rate == 0:
+            rs.sample_rate = rate
+            if rs.pcm_slot is not None:
+                rs.pcm_slot.rate = rate      # HUB_MAX_UTTERANCE_S in this rate's samples
+            return
+        self.stats["rate_changes"] += 1
+        if not rs.rate_change_logged:
+            rs.rate_change_logged = True
+            hublog.log_warn("sample rate changed mid-stream (the first rate stands)",
+                            relay_id=rs.relay_id, sample_rate=rs.sample_rate, chunk_rate=rate)
 
     async def _await_result(self, rs: RelayStream, stream: "_ContextWriter") -> None:
         if rs.status == RelayStatus.CONTENDING:

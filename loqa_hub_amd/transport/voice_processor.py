@@ -136,13 +136,16 @@ class GPUVoiceProcessor:
         the relay's raw samples (skips the float round trip); ``pcm_slot``: the
         pinned stager slot its chunks were appended to as they arrived (the
         STT upload copies it straight to HBM). Concurrent calls are
-        micro-batched by the pipeline (STT batch, continuous LLM batch)."""
+        micro-batched by the pipeline (STT batch, continuous LLM batch).
+        ``sample_rate``: the rate of the samples; other than 16 kHz they are
+        resampled on the device by the STT upload."""
         from ..engine.pipeline import PipelineJob
         if pcm_slot is not None:
             pcm = np.zeros(0, np.int16)
         else:
             pcm = pcm16 if pcm16 is not None else float_to_pcm16(audio)
-        j = PipelineJob(relay_id, request_id, pcm, transcript_hint, staged=pcm_slot)
+        j = PipelineJob(relay_id, request_id, pcm, transcript_hint, staged=pcm_slot,
+                        sample_rate=sample_rate or 16000)
         speech = None
         if self.progressive:
             from ..streaming.progressive import ProgressiveSpeech
