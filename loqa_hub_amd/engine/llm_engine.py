@@ -14,7 +14,8 @@ Step anatomy (all on the compute stream):
             grammar-masked argmax (one mask row per sequence).  Decode steps
             are replayed from HIP graphs bucketed by (seqs, tokens).
 Host work per step is the grammar cursor advance (a few dict lookups per
-sequence) plus one small pinned H2D copy of the step metadata.
+sequence) plus the step metadata, staged in a pinned ring the step graph reads
+(engine/step_io.py).
 """
 from __future__ import annotations
 
@@ -35,6 +36,7 @@ from .batching import MPAD_PLAN, join_futures, plan_step, plan_step_mpad
 from ..models.llama import LlamaModel, LlamaWeights, StepMeta, TPGroup
 from .grammar import GrammarState, GrammarTables
 from .kv_cache import PagedKVCache
+from .step_io import StepIO, StepLayout, decode_buckets, fill_meta, step_shapes, to_device
 from .tokenizer import get_tokenizer
 from ..parallel.custom_allreduce import ERR_TOKEN, CollectiveError
 
@@ -72,7 +74,13 @@ def _bucket(n: int, buckets: list[int]) -> int:
 
 class LLMEngine:
     SEQ_BUCKETS = [1, 2, 4, 8, 16, 32, 64, 128]
-    RES_SLOTS = 3       # result ring slots (>= steps in flight + 1)
+    # int32 metadata of a captured decode step, in staging order (engine/step_io.py)
+    STEP_FIELDS = ("tokens", "positions", "slots", "cu_q", "ctx_lens", "block_tables",
+                   "mask_rows", "src", "row_slot")
+
+    @classmethod
+    def step_layout(cls, B_pad: int, T_pad: int, max_blocks: int) -> StepLayout:
+        return StepLayout(step_shapes(cls.STEP_FIELDS, B_pad, T_pad, max_blocks), max(16, B_pad))
 
     def __init__(self, cfg: LlamaConfig, device, *, seed: int = 0, max_seqs: int = 64,
                  max_seq_len: int = 1024, block_size: int = 16, num_blocks: int | None = None,
@@ -176,19 +184,11 @@ class LLMEngine:
         # (+ one trash slot for padding rows), free sequence slots
         self.last_tok = torch.zeros(max_seqs + 1, dtype=torch.int32, device=self.device)
         self._free_seq_slots = list(range(max_seqs))
-        if self.use_graphs:
-            # step I/O without copy-engine operations between step graphs
-            # (elementwise.hip step_fetch / step_publish): a 2-slot pinned
-            # staging ring for step metadata, a 3-slot pinned result ring, and
-            # a device counter of launched step graphs that picks the slots
-            b_max = _bucket(max(1, max_seqs), self.SEQ_BUCKETS)
-            self._n32_max = 4 * ops.MPADS[-1] + 4 * b_max + 1 + b_max * self.max_blocks
-            self._n64_max = max(16, b_max)
-            self._stage32 = torch.zeros(2, self._n32_max, dtype=torch.int32).pin_memory()
-            self._stage64 = torch.zeros(2, self._n64_max, dtype=torch.int64).pin_memory()
-            self._res_ring = torch.zeros(self.RES_SLOTS, 256, dtype=torch.int32).pin_memory()
-            self._step_ctr = torch.zeros(1, dtype=torch.int32, device=self.device)
-            self._step_no = 0
+        # step I/O of the captured steps without copy-engine operations between
+        # step graphs (engine/step_io.py); its staging rows hold the largest bucket
+        self.io = StepIO(self.device, self.step_layout(
+            _bucket(max(1, max_seqs), self.SEQ_BUCKETS), ops.MPADS[-1], self.max_blocks),
+            self.last_tok) if self.use_graphs else None
         self.pipelined = self.use_graphs and os.environ.get("LOQA_LLM_PIPELINE", "1") != "0"
         self._pl = None
         # set once warmup_graphs() has captured every reachable bucket: from
@@ -219,49 +219,18 @@ class LLMEngine:
               B_pad: int | None = None, T_pad: int | None = None,
               out: dict | None = None) -> tuple[StepMeta, dict]:
         """Host metadata of one step; ``out`` = preallocated (pinned) numpy views
-        to fill in place (the graph path: one H2D copy per step, no allocation)."""
+        to fill in place and return (the graph path: a staging row, no allocation)."""
         B = len(seqs)
-        T = sum(len(f) for f in feeds)
         B_pad = B_pad or B
-        T_pad = T_pad or T
-        if out is not None:
-            tokens, positions, slots = out["tokens"], out["positions"], out["slots"]
-            cu, ctx, bt, lidx = out["cu_q"], out["ctx_lens"], out["block_tables"], out["logit_idx"]
-        else:
-            tokens = np.zeros(T_pad, np.int32)
-            positions = np.zeros(T_pad, np.int32)
-            slots = np.full(T_pad, -1, np.int32)
-            cu = np.zeros(B_pad + 1, np.int32)
-            ctx = np.zeros(B_pad, np.int32)
-            bt = np.zeros((B_pad, self.max_blocks), np.int32)
-            lidx = np.zeros(max(16, B_pad) if decode else B_pad, np.int64)
-        tokens.fill(0)
-        if T:
-            tokens[:T] = [t for f in feeds for t in f]
-        rc = self.kv.pool.step_meta([r.seq_id for r in seqs], [len(f) for f in feeds], B_pad,
-                                    T_pad, self.max_blocks, positions, slots, cu, ctx, bt, lidx)
-        if rc == -2:
-            raise RuntimeError("KV cache exhausted")
-        if rc != 0:
-            raise RuntimeError(f"step metadata failed ({rc})")
+        T_pad = T_pad or sum(len(f) for f in feeds)
+        host = fill_meta(self.kv.pool, [r.seq_id for r in seqs], feeds, B_pad, T_pad,
+                         self.max_blocks, max(16, B_pad) if decode else B_pad, out)
         max_q = max([len(f) for f in feeds] + [1])
-        max_ctx = max(int(ctx[:B].max()) if B else 1, 1)
-        host = {"tokens": tokens, "positions": positions, "slots": slots, "cu_q": cu,
-                "ctx_lens": ctx, "block_tables": bt, "logit_idx": lidx}
+        max_ctx = max(int(host["ctx_lens"][:B].max()) if B else 1, 1)
         return max_q, max_ctx, host
 
     def _to_device(self, host: dict, dst: dict | None = None) -> dict:
-        out = {}
-        for k, a in host.items():
-            t = torch.from_numpy(a)
-            if self.is_gpu:
-                t = t.pin_memory()
-            if dst is not None:
-                dst[k].copy_(t, non_blocking=True)
-                out[k] = dst[k]
-            else:
-                out[k] = t.to(self.device, non_blocking=True)
-        return out
+        return to_device(host, self.device, dst)
 
     # ---------------------------------------------------- compact sampling head
     # "auto" uses the compact head while it is at most this share of the
@@ -417,75 +386,16 @@ class LLMEngine:
         ctx = ctx or self.max_seq_len
         key = (B_pad, T_pad, ctx)
         g = self._graphs.get(key)
-        if g is not None:
-            return g
-        # all int32 metadata lives in ONE device buffer, int64 logit rows in a
-        # second; the graph's first node fills both from the pinned staging ring
-        shapes = {"tokens": (T_pad,), "positions": (T_pad,), "slots": (T_pad,),
-                  "cu_q": (B_pad + 1,), "ctx_lens": (B_pad,),
-                  "block_tables": (B_pad, self.max_blocks), "mask_rows": (B_pad,),
-                  "src": (T_pad,), "row_slot": (B_pad,)}
-        n32 = sum(int(np.prod(v)) for v in shapes.values())
-        L = max(16, B_pad)
-        assert n32 <= self._n32_max and L <= self._n64_max and B_pad <= 256
-        d32 = torch.zeros(n32, dtype=torch.int32, device=self.device)
-        d64 = torch.zeros(L, dtype=torch.int64, device=self.device)
-        dev, off = {}, 0
-        for k, shp in shapes.items():
-            n = int(np.prod(shp))
-            dev[k] = d32[off:off + n].view(*shp)
-            off += n
-        dev["slots"].fill_(-1)
-        dev["src"].fill_(-1)
-        dev["row_slot"].fill_(self.max_seqs)
-        dev["logit_idx"] = d64
-        meta = self._build_meta(dev, self.max_decode_q, ctx, True)
-        # warm up (allocator + kernels) on a side stream, then capture; the
-        # warm-up runs the body only (the I/O nodes would advance the counter)
-        s = torch.cuda.Stream(self.device)
-        s.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(s):
-            out = self._step_body(meta, dev)
-        torch.cuda.current_stream(self.device).wait_stream(s)
-        graph = torch.cuda.CUDAGraph()
-        k = ops._lib.kernels()
-        # thread-local capture: the other GPU worker thread keeps running
-        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-            st = ops._lib.stream_ptr(d32)
-            src_off = dev["src"].data_ptr() // 4 - d32.data_ptr() // 4
-            ops._lib.check(k.loqa_step_fetch(
-                ops._lib.ptr(d32), self._stage32.data_ptr(), n32, self._n32_max, ops._lib.ptr(d64),
-                self._stage64.data_ptr(), L, self._n64_max, ops._lib.ptr(self._step_ctr), T_pad,
-                src_off, ops._lib.ptr(self.last_tok), st), "step_fetch")
-            out = self._step_body(meta, dev, device_io=True)
-            ops._lib.check(k.loqa_step_publish(
-                ops._lib.ptr(out), B_pad, self._res_ring.data_ptr(), self._res_ring.shape[1],
-                self.RES_SLOTS, ops._lib.ptr(self._step_ctr), ops._lib.ptr(dev["row_slot"]),
-                ops._lib.ptr(self.last_tok), st), "step_publish")
-        g = {"graph": graph, "dev": dev, "out": out, "shapes": shapes, "n32": n32, "L": L}
-        self._graphs[key] = g
+        if g is None:
+            def body(dev, device_io=True):
+                meta = self._build_meta(dev, self.max_decode_q, ctx, True)
+                return self._step_body(meta, dev, device_io)
+            # the warm-up runs the eager step (its gather / store kernels are
+            # what an uncaptured bucket launches while serving)
+            g = self._graphs[key] = self.io.capture(
+                self.step_layout(B_pad, T_pad, self.max_blocks), T_pad, body,
+                warm=lambda dev: body(dev, False))
         return g
-
-    def _stage(self, g: dict) -> dict:
-        """Numpy views of the staging slot of the NEXT step graph launch, in
-        graph ``g``'s metadata layout."""
-        slot = self._step_no % 2
-        hn, out, off = self._stage32[slot].numpy(), {}, 0
-        for k, shp in g["shapes"].items():
-            n = int(np.prod(shp))
-            out[k] = hn[off:off + n].reshape(shp)
-            off += n
-        out["logit_idx"] = self._stage64[slot].numpy()[: g["L"]]
-        return out
-
-    def _replay(self, g: dict) -> int:
-        """Launch a step graph whose staging slot is filled; returns the result
-        ring slot its sampled tokens will land in."""
-        rslot = self._step_no % self.RES_SLOTS
-        g["graph"].replay()
-        # wraps like the device counter (step_publish): 2 staging x RES_SLOTS
-        self._step_no = (self._step_no + 1) % (2 * self.RES_SLOTS)
-        return rslot
 
     def _step_body(self, meta: StepMeta, dev: dict, device_io: bool = False) -> torch.Tensor:
         """One captured decode step: tokens whose ``src`` >= 0 are taken from
@@ -494,7 +404,7 @@ class LLMEngine:
         step's tokens), then forward + masked argmax, then each row's sampled
         token is stored under its sequence slot (``row_slot``; padding rows
         write a trash slot). ``device_io``: the graph's fetch / publish nodes
-        do the gather and the store (LLMEngine._decode_graph)."""
+        do the gather and the store (engine/step_io.py)."""
         if device_io:
             return self._forward_sample(meta, dev["mask_rows"])
         src = dev["src"]
@@ -522,23 +432,12 @@ class LLMEngine:
             # can take longer than a bounded collective wait)
             import torch.distributed as dist
             dist.barrier(group=self.tp.group)
-        n = 0
-        b_max = _bucket(max(1, self.max_seqs), self.SEQ_BUCKETS)
-        for b in self.SEQ_BUCKETS:
-            if b > b_max:
-                break
-            t_min = ops.mpad_for(min(self.step_tokens, b // 2 + 1))   # T >= B > b/2
-            t_max = ops.mpad_for(min(self.step_tokens, b * self.max_decode_q))
-            for t in ops.MPADS:
-                if t > t_max:
-                    break
-                if t < t_min:
-                    continue
-                for c in range(self.CTX_BUCKET, self.max_seq_len + self.CTX_BUCKET, self.CTX_BUCKET):
-                    self._decode_graph(b, t, min(c, self.max_seq_len))
-                    n += 1
+        buckets = decode_buckets(self.SEQ_BUCKETS, self.max_seqs, self.step_tokens,
+                                 self.max_decode_q, self.CTX_BUCKET, self.max_seq_len)
+        for b, t, c in buckets:
+            self._decode_graph(b, t, c)
         self._graphs_frozen = True
-        return n
+        return len(buckets)
 
     # ------------------------------------------------------------ generate
     def submit(self, req: GenRequest) -> GenRequest:
@@ -688,17 +587,17 @@ class LLMEngine:
             elif g is None:
                 g = self._decode_graph(B_pad, T_pad, C)
         if self.use_graphs and g is not False:
-            hb = self._stage(g)
+            hb = self.io.stage(g)
             self._meta(live, feeds, True, B_pad, T_pad, out=hb)
             hb["mask_rows"].fill(0)
             hb["mask_rows"][:B] = rows
             hb["src"].fill(-1)
-            hb["row_slot"].fill(self.max_seqs)
+            hb["row_slot"].fill(self.io.trash)
             t1 = time.perf_counter()
-            rslot = self._replay(g)
+            rslot = self.io.replay(g)
             t15 = time.perf_counter()
             torch.cuda.current_stream(self.device).synchronize()
-            nxt = self._res_ring[rslot, :B].numpy().copy()
+            nxt = self.io.result(rslot, B)
             t2 = time.perf_counter()
             self.stats["host_pre_s"] += t1 - t0
             self.stats["replay_call_s"] += t15 - t1

@@ -19,9 +19,9 @@ serving pipeline. Here step j+1 is launched while step j still runs:
   discarded: its KV length is rolled back (``pool.truncate``) and the correct
   tokens are fed in step j+2 at the same positions, overwriting the garbage.
 
-Streams order everything else: a step's H2D metadata copy runs after the
-previous step, its result copy before the next one, so two pinned staging
-buffers per graph and one result buffer per in-flight step suffice.
+Step I/O - the pinned staging and result rings, the device counter that picks
+their rows, ``DEV`` and the staging of device-fed tokens - is
+``engine/step_io.py``, shared with the Whisper decoder's pipeline.
 """
 from __future__ import annotations
 
@@ -33,8 +33,7 @@ import torch
 
 from .. import ops
 from .batching import MPAD_PLAN, plan_step, plan_step_mpad
-
-DEV = -1   # feed placeholder: "the token this sequence sampled in its previous step"
+from .step_io import DEV, StepIO, stage_feeds
 
 
 class _Step:
@@ -60,7 +59,7 @@ class DecodePipeline:
         # test hook: treat this fraction of generic tokens as mispredicted
         self.force_mispredict = 0.0
         self._rng = np.random.default_rng(0)
-        assert not eng.use_graphs or eng.RES_SLOTS >= self.DEPTH + 1
+        StepIO.check_depth(self.DEPTH)
 
     # ----------------------------------------------------------- helpers
     def admit(self, r) -> None:
@@ -181,31 +180,23 @@ class DecodePipeline:
         sid = self.next_id
         self.next_id += 1
         slot_of = [r.pl_slot for r in rows]
-        toks = [0 if t == DEV else t for f in feeds for t in f]
-        src = []
-        for f, sl in zip(feeds, slot_of):
-            src += [sl if t == DEV else -1 for t in f]
         mrows = [e["row"] for e in entries]
         if g is not None:
-            # the staging slot written here was last read by the step two
+            # the staging row written here was last read by the step two
             # launches back, which has retired
-            host = eng._stage(g)
-            eng._meta(rows, [[0] * len(f) for f in feeds], True, B_pad, T_pad, out=host)
-            host["tokens"][:T] = toks
-            host["src"].fill(-1)
-            host["src"][:T] = src
+            host = eng.io.stage(g)
+            eng._meta(rows, feeds, True, B_pad, T_pad, out=host)
+            stage_feeds(host, feeds, slot_of, eng.io.trash)
             host["mask_rows"].fill(0)
             host["mask_rows"][:B] = mrows
-            host["row_slot"].fill(eng.max_seqs)
-            host["row_slot"][:B] = slot_of
             t1 = time.perf_counter()
-            rslot = eng._replay(g)
+            rslot = eng.io.replay(g)
             ev = torch.cuda.Event()
             ev.record()
             eng.stats["host_pre_s"] += t1 - t0
-            st = _Step(sid, rows, B, eng._res_ring[rslot], ev, g, entries)
+            st = _Step(sid, rows, B, rslot, ev, g, entries)
         else:
-            st = self._run_eager(sid, rows, feeds, toks, src, mrows, slot_of, entries, B_pad, T_pad)
+            st = self._run_eager(sid, rows, feeds, mrows, slot_of, entries, B_pad, T_pad)
         for r, e in zip(rows, entries):
             r.pl_fl.append(e)
             if e["spec"]:
@@ -226,24 +217,19 @@ class DecodePipeline:
         finally:
             eng.use_graphs = use
 
-    def _run_eager(self, sid, rows, feeds, toks, src, mrows, slot_of, entries, B_pad, T_pad):
+    def _run_eager(self, sid, rows, feeds, mrows, slot_of, entries, B_pad, T_pad):
         eng = self.eng
-        max_q, max_ctx, host = eng._meta(rows, [[0] * len(f) for f in feeds], True, B_pad, T_pad)
-        T = len(toks)
-        host["tokens"][:T] = toks
-        s = np.full(T_pad, -1, np.int32)
-        s[:T] = src
-        host["src"] = s
+        max_q, max_ctx, host = eng._meta(rows, feeds, True, B_pad, T_pad)
+        host["src"] = np.empty(T_pad, np.int32)
+        host["row_slot"] = np.empty(B_pad, np.int32)
+        stage_feeds(host, feeds, slot_of, eng.max_seqs)
         mr = np.zeros(B_pad, np.int32)
         mr[:len(mrows)] = mrows
         host["mask_rows"] = mr
-        rs = np.full(B_pad, eng.max_seqs, np.int32)
-        rs[:len(slot_of)] = slot_of
-        host["row_slot"] = rs
         dev = eng._to_device(host)
         meta = eng._build_meta(dev, max_q, max_ctx, True)
         out = eng._step_body(meta, dev)
-        res = out[:B_pad].to("cpu", torch.int32)
+        res = out[:B_pad].to("cpu", torch.int32).numpy()
         return _Step(sid, rows, len(rows), res, None, None, entries)
 
     # ------------------------------------------------------------ retire
@@ -253,7 +239,8 @@ class DecodePipeline:
         if st.event is not None:
             st.event.synchronize()
         t1 = time.perf_counter()
-        nxt = st.out[: st.B].numpy().copy()
+        # a graph step's ``out`` is its result ring row, an eager step's its tokens
+        nxt = eng.io.result(st.out, st.B) if st.event is not None else st.out[: st.B]
         eng.stats["gpu_wait_s"] += t1 - t0
         now = time.perf_counter()
         for b, r in enumerate(st.rows):

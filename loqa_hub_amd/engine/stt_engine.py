@@ -28,6 +28,7 @@ from ..models.whisper import WhisperModel, WhisperWeights, decode_step_fast, dec
 from ..utils.tracing import tracer
 from .batching import join_futures, plan_step
 from .kv_cache import PagedKVCache
+from .step_io import StepIO, StepLayout, decode_buckets, fill_meta, step_shapes, to_device
 from .tokenizer import get_tokenizer
 
 log = logging.getLogger("loqa.stt")
@@ -106,7 +107,14 @@ class STTRequest:
 class STTEngine:
     SEQ_BUCKETS = [1, 2, 4, 8, 16, 32, 64, 128]
     SPLIT_KEYS = 128
-    RES_SLOTS = 3       # result ring slots (>= steps in flight + 1)
+    # int32 metadata of a captured decoder step, in staging order (engine/step_io.py)
+    STEP_FIELDS = ("tokens", "positions", "slots", "cu_q", "ctx_lens", "block_tables",
+                   "enc_starts", "enc_lens", "src", "row_slot")
+
+    @classmethod
+    def step_layout(cls, B_pad: int, T_pad: int, max_blocks: int) -> StepLayout:
+        return StepLayout(step_shapes(cls.STEP_FIELDS, B_pad, T_pad, max_blocks),
+                          max(16, ops.mpad_for(B_pad)))
 
     def __init__(self, cfg: WhisperConfig, device, *, seed: int = 0, max_batch: int = 64,
                  block_size: int = 16, use_graphs: bool = True, fast_decode: bool = True,
@@ -205,23 +213,15 @@ class STTEngine:
                                                   ops.MPADS[-2]))
         self._rr = 0
         if self.use_graphs:
-            # step I/O without copy-engine operations between step graphs (as the
-            # LLM engine: elementwise.hip step_fetch / step_publish): a 2-slot
-            # pinned staging ring for the step metadata, a result ring, a device
-            # counter of launched step graphs, and the last token of every
-            # cross-attention slot (+ a trash slot) for device-fed greedy steps
+            # step I/O without copy-engine operations between step graphs, as the
+            # LLM engine (engine/step_io.py): its staging rows hold the largest
+            # bucket; the last token of every cross-attention slot (+ a trash
+            # slot) feeds the device-fed greedy steps, and with ``token_logprobs``
+            # the tokens' log-probabilities are published beside them
             b_max = next((b for b in self.SEQ_BUCKETS if b >= max_batch), self.SEQ_BUCKETS[-1])
-            self._n32_max = 4 * ops.MPADS[-1] + 6 * b_max + 1 + b_max * self.max_blocks
-            self._n64_max = max(16, ops.mpad_for(min(b_max, ops.MPADS[-1])))
-            self._stage32 = torch.zeros(2, self._n32_max, dtype=torch.int32).pin_memory()
-            self._stage64 = torch.zeros(2, self._n64_max, dtype=torch.int64).pin_memory()
-            self._res_ring = torch.zeros(self.RES_SLOTS, 256, dtype=torch.int32).pin_memory()
-            # the steps' token log-probabilities, same slots (loqa_step_publish_lp)
-            self._res_lp_ring = torch.zeros(self.RES_SLOTS, 256, dtype=torch.float32).pin_memory() \
-                if token_logprobs else None
-            self._step_ctr = torch.zeros(1, dtype=torch.int32, device=self.device)
-            self._step_no = 0
             self.last_tok = torch.zeros(max_batch + 1, dtype=torch.int32, device=self.device)
+            self.io = StepIO(self.device, self.step_layout(b_max, ops.MPADS[-1], self.max_blocks),
+                             self.last_tok, logprobs=token_logprobs)
         # two decoder steps in flight (the host prepares step j+1 while step j
         # runs); LOQA_STT_PIPELINE=0: one synchronous step at a time
         self.pipelined = self.use_graphs and os.environ.get("LOQA_STT_PIPELINE", "1") != "0"
@@ -379,55 +379,28 @@ class STTEngine:
         return self.xkv
 
     def _host_meta(self, live: list[STTRequest], B_pad: int, T_pad: int,
-                   out: dict | None = None) -> tuple[int, dict]:
+                   out: dict | None = None, feeds: list | None = None) -> tuple[int, dict]:
+        """Host metadata of one step feeding ``feeds`` (default: every
+        request's ``feed``); ``out`` = preallocated views (a staging row) to
+        fill in place and return."""
         T_enc = self.cfg.n_audio_ctx
-        L = max(16, ops.mpad_for(B_pad))
-        if out is not None:  # preallocated pinned views (graph path), filled below
-            tokens, positions, slots = out["tokens"], out["positions"], out["slots"]
-            cu, ctx, bt = out["cu_q"], out["ctx_lens"], out["block_tables"]
-            enc_starts, enc_lens, lidx = out["enc_starts"], out["enc_lens"], out["logit_idx"]
-        else:
-            tokens = np.zeros(T_pad, np.int32)
-            positions = np.zeros(T_pad, np.int32)
-            slots = np.full(T_pad, -1, np.int32)
-            cu = np.zeros(B_pad + 1, np.int32)
-            ctx = np.zeros(B_pad, np.int32)
-            bt = np.zeros((B_pad, self.max_blocks), np.int32)
-            enc_starts = np.zeros(B_pad, np.int32)
-            enc_lens = np.zeros(B_pad, np.int32)
-            lidx = np.zeros(L, np.int64)
-        T = sum(len(r.feed) for r in live)
-        tokens.fill(0)
-        if T:
-            tokens[:T] = [t for r in live for t in r.feed]
-        rc = self.kv.pool.step_meta([r.seq_id for r in live], [len(r.feed) for r in live], B_pad,
-                                    T_pad, self.max_blocks, positions, slots, cu, ctx, bt, lidx)
-        if rc == -2:
-            raise RuntimeError("STT KV cache exhausted")
-        if rc != 0:
-            raise RuntimeError(f"step metadata failed ({rc})")
+        if feeds is None:
+            feeds = [r.feed for r in live]
+        host = fill_meta(self.kv.pool, [r.seq_id for r in live], feeds, B_pad, T_pad,
+                         self.max_blocks, max(16, ops.mpad_for(B_pad)), out, "STT KV cache")
+        if out is None:
+            host["enc_starts"] = np.zeros(B_pad, np.int32)
+            host["enc_lens"] = np.zeros(B_pad, np.int32)
         n = len(live)
+        enc_starts, enc_lens = host["enc_starts"], host["enc_lens"]
         enc_starts[:n] = [r.slot * T_enc for r in live]
         enc_starts[n:] = 0
         enc_lens[:n] = T_enc
         enc_lens[n:] = 0
-        max_q = max([len(r.feed) for r in live] + [1])
-        return max_q, {"tokens": tokens, "positions": positions, "slots": slots, "cu_q": cu,
-                       "ctx_lens": ctx, "block_tables": bt, "enc_starts": enc_starts,
-                       "enc_lens": enc_lens, "logit_idx": lidx}
+        return max([len(f) for f in feeds] + [1]), host
 
     def _dev(self, host: dict, dst: dict | None = None) -> dict:
-        out = {}
-        for k, a in host.items():
-            t = torch.from_numpy(a)
-            if self.is_gpu:
-                t = t.pin_memory()
-            if dst is not None:
-                dst[k].copy_(t, non_blocking=True)
-                out[k] = dst[k]
-            else:
-                out[k] = t.to(self.device, non_blocking=True)
-        return out
+        return to_device(host, self.device, dst)
 
     def _self_splits(self, ctx: int | None) -> int:
         """Self-attention key splits for a context bound (graph bucket)."""
@@ -473,77 +446,12 @@ class STTEngine:
         node publishes the sampled tokens to the pinned result ring."""
         key = (B_pad, T_pad, ctx)
         g = self._graphs.get(key)
-        if g is not None:
-            return g
-        shapes = {"tokens": (T_pad,), "positions": (T_pad,), "slots": (T_pad,),
-                  "cu_q": (B_pad + 1,), "ctx_lens": (B_pad,),
-                  "block_tables": (B_pad, self.max_blocks), "enc_starts": (B_pad,),
-                  "enc_lens": (B_pad,), "src": (T_pad,), "row_slot": (B_pad,)}
-        n32 = sum(int(np.prod(v)) for v in shapes.values())
-        L = max(16, ops.mpad_for(B_pad))
-        assert n32 <= self._n32_max and L <= self._n64_max and B_pad <= 256
-        d32 = torch.zeros(n32, dtype=torch.int32, device=self.device)
-        d64 = torch.zeros(L, dtype=torch.int64, device=self.device)
-        dev, off = {}, 0
-        for k, shp in shapes.items():
-            n = int(np.prod(shp))
-            dev[k] = d32[off:off + n].view(*shp)
-            off += n
-        dev["slots"].fill_(-1)
-        dev["src"].fill_(-1)
-        dev["row_slot"].fill_(self.max_batch)
-        dev["logit_idx"] = d64
-        max_q = max(1, min(len(self.sot), T_pad))
-        s = torch.cuda.Stream(self.device)
-        s.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(s):
-            self._fast_forward(dev, max_q, B_pad, ctx)
-        torch.cuda.current_stream(self.device).wait_stream(s)
-        graph = torch.cuda.CUDAGraph()
-        k = ops._lib.kernels()
-        lib = ops._lib
-        # thread-local capture: the other GPU worker thread keeps running
-        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-            st = lib.stream_ptr(d32)
-            src_off = dev["src"].data_ptr() // 4 - d32.data_ptr() // 4
-            lib.check(k.loqa_step_fetch(
-                lib.ptr(d32), self._stage32.data_ptr(), n32, self._n32_max, lib.ptr(d64),
-                self._stage64.data_ptr(), L, self._n64_max, lib.ptr(self._step_ctr), T_pad, src_off,
-                lib.ptr(self.last_tok), st), "step_fetch")
-            out = self._fast_forward(dev, max_q, B_pad, ctx)
-            if self.token_logprobs:
-                lib.check(k.loqa_step_publish_lp(
-                    lib.ptr(out[0]), lib.ptr(out[1]), B_pad, self._res_ring.data_ptr(),
-                    self._res_ring.shape[1], self._res_lp_ring.data_ptr(),
-                    self._res_lp_ring.shape[1], self.RES_SLOTS, lib.ptr(self._step_ctr),
-                    lib.ptr(dev["row_slot"]), lib.ptr(self.last_tok), st), "step_publish_lp")
-            else:
-                lib.check(k.loqa_step_publish(
-                    lib.ptr(out), B_pad, self._res_ring.data_ptr(), self._res_ring.shape[1],
-                    self.RES_SLOTS, lib.ptr(self._step_ctr), lib.ptr(dev["row_slot"]),
-                    lib.ptr(self.last_tok), st), "step_publish")
-        g = {"graph": graph, "dev": dev, "out": out, "shapes": shapes, "n32": n32, "L": L}
-        self._graphs[key] = g
+        if g is None:
+            max_q = max(1, min(len(self.sot), T_pad))
+            g = self._graphs[key] = self.io.capture(
+                self.step_layout(B_pad, T_pad, self.max_blocks), T_pad,
+                lambda dev: self._fast_forward(dev, max_q, B_pad, ctx))
         return g
-
-    def _stage(self, g: dict) -> dict:
-        """Numpy views of the staging slot of the NEXT step-graph launch."""
-        slot = self._step_no % 2
-        hn, out, off = self._stage32[slot].numpy(), {}, 0
-        for k, shp in g["shapes"].items():
-            n = int(np.prod(shp))
-            out[k] = hn[off:off + n].reshape(shp)
-            off += n
-        out["logit_idx"] = self._stage64[slot].numpy()[: g["L"]]
-        return out
-
-    def _replay(self, g: dict) -> int:
-        """Launch a step graph whose staging slot is filled; returns the result
-        ring slot its tokens land in."""
-        rslot = self._step_no % self.RES_SLOTS
-        g["graph"].replay()
-        self._step_no = (self._step_no + 1) % (2 * self.RES_SLOTS)   # wraps as the device counter
-        return rslot
 
     # encoder graphs for batches of up to this many utterances (0: eager encoder)
     ENC_GRAPH_MAX = 4
@@ -595,23 +503,12 @@ class STTEngine:
             for b in range(1, min(self.ENC_GRAPH_MAX, self.max_batch) + 1):
                 self._enc_graph(b)
                 n += 1
-        n_sot = len(self.sot)
-        b_max = next((b for b in self.SEQ_BUCKETS if b >= self.max_batch), self.SEQ_BUCKETS[-1])
-        for b in self.SEQ_BUCKETS:
-            if b > b_max:
-                break
-            t_min = ops.mpad_for(min(self.step_tokens, b // 2 + 1))   # T >= B > b/2
-            t_max = ops.mpad_for(min(self.step_tokens, b * n_sot))
-            for t in ops.MPADS:
-                if t > t_max:
-                    break
-                if t < t_min:
-                    continue
-                for c in range(self.SPLIT_KEYS, self.cfg.n_text_ctx + self.SPLIT_KEYS, self.SPLIT_KEYS):
-                    self._graph(b, t, min(c, self.cfg.n_text_ctx))
-                    n += 1
+        buckets = decode_buckets(self.SEQ_BUCKETS, self.max_batch, self.step_tokens, len(self.sot),
+                                 self.SPLIT_KEYS, self.cfg.n_text_ctx)
+        for b, t, c in buckets:
+            self._graph(b, t, c)
         self._graphs_frozen = True
-        return n
+        return n + len(buckets)
 
     def _step(self, live: list[STTRequest]):
         """One decoder step for every live request (its ``feed`` tokens): the
@@ -626,16 +523,14 @@ class STTEngine:
             if self.use_graphs and ((B_pad, T_pad, C) in self._graphs or not self._graphs_frozen):
                 t0 = time.perf_counter()
                 g = self._graph(B_pad, T_pad, C)
-                hb = self._stage(g)
+                hb = self.io.stage(g)
                 self._host_meta(live, B_pad, T_pad, out=hb)
                 hb["src"].fill(-1)
-                hb["row_slot"].fill(self.max_batch)
+                hb["row_slot"].fill(self.io.trash)
                 t1 = time.perf_counter()
-                rslot = self._replay(g)
+                rslot = self.io.replay(g)
                 torch.cuda.current_stream(self.device).synchronize()
-                out = self._res_ring[rslot, :B].numpy().copy()
-                if self.token_logprobs:
-                    out = out, self._res_lp_ring[rslot, :B].numpy().copy()
+                out = self.io.result(rslot, B)
                 self.stats["host_pre_s"] += t1 - t0
                 self.stats["gpu_wait_s"] += time.perf_counter() - t1
                 return out

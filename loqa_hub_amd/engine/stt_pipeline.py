@@ -15,7 +15,8 @@ launched while step j still runs, as the LLM engine does
   and is discarded (its KV / last-token writes are stream-ordered before any
   reuse of the blocks or the slot).
 
-Step I/O is the engine's pinned staging / result rings and device counter.
+Step I/O (pinned staging / result rings, device counter, ``DEV`` staging) is
+``engine/step_io.py``, shared with the LLM engine's pipeline.
 """
 from __future__ import annotations
 
@@ -26,16 +27,16 @@ import numpy as np
 import torch
 
 from .. import ops
-
-DEV = -1   # feed placeholder: the token this request sampled in its previous step
+from .step_io import DEV, StepIO, stage_feeds
 
 
 class _Step:
-    __slots__ = ("rows", "B", "out", "event", "entries", "lp")
+    __slots__ = ("rows", "B", "out", "event", "entries")
 
-    def __init__(self, rows, B, out, event, entries, lp=None):
+    def __init__(self, rows, B, out, event, entries):
+        # out: a graph step's result ring row; a synchronous step's result
+        # (tokens, with the engine's token_logprobs (tokens, log-probabilities))
         self.rows, self.B, self.out, self.event, self.entries = rows, B, out, event, entries
-        self.lp = lp        # the step's token log-probabilities (engine token_logprobs)
 
 
 class STTPipeline:
@@ -51,7 +52,7 @@ class STTPipeline:
         # replay call alone: where a step-to-step gap on the STT stream comes from
         for k in ("pl_launch_s", "pl_replay_s"):
             self.stats.setdefault(k, 0.0)
-        assert eng.RES_SLOTS >= self.DEPTH + 1
+        StepIO.check_depth(self.DEPTH)
 
     # -------------------------------------------------------------- helpers
     @staticmethod
@@ -138,25 +139,11 @@ class STTPipeline:
         if (B_pad, T_pad, C) not in eng._graphs and eng._graphs_frozen:
             return self._launch_sync(rows, feeds)
         g = eng._graph(B_pad, T_pad, C)
-        hb = eng._stage(g)
-        saved = [r.feed for r in rows]
-        for r, f in zip(rows, feeds):
-            r.feed = [0 if t == DEV else t for t in f]
-        eng._host_meta(rows, B_pad, T_pad, out=hb)
-        for r, f in zip(rows, saved):
-            r.feed = f
-        src = hb["src"]
-        src.fill(-1)
-        i = 0
-        for r, f in zip(rows, feeds):
-            for t in f:
-                if t == DEV:
-                    src[i] = r.slot
-                i += 1
-        hb["row_slot"].fill(eng.max_batch)
-        hb["row_slot"][:B] = [r.slot for r in rows]
+        hb = eng.io.stage(g)
+        eng._host_meta(rows, B_pad, T_pad, out=hb, feeds=feeds)
+        stage_feeds(hb, feeds, [r.slot for r in rows], eng.io.trash)
         t_r = time.perf_counter()
-        rslot = eng._replay(g)
+        rslot = eng.io.replay(g)
         self.stats["pl_replay_s"] += time.perf_counter() - t_r
         ev = torch.cuda.Event()
         ev.record()
@@ -167,8 +154,7 @@ class STTPipeline:
             r.pl_fl += 1
             if sp:
                 self.stats["pl_spec"] += 1
-        lp = eng._res_lp_ring[rslot] if eng.token_logprobs else None
-        self.inflight.append(_Step(rows, B, eng._res_ring[rslot], ev, entries, lp))
+        self.inflight.append(_Step(rows, B, rslot, ev, entries))
         self.stats["pl_steps"] += 1
         eng.stats["decode_steps"] += 1
         return True
@@ -181,11 +167,8 @@ class STTPipeline:
         saved = [r.feed for r in rows]
         for r, f in zip(rows, feeds):
             r.feed = f
-        out = self.eng._step(rows)
-        lp = None
-        if self.eng.token_logprobs:
-            out, lp = out
-            lp = torch.from_numpy(np.asarray(lp, np.float32))
+        res = self.eng._step(rows)
+        out = res[0] if self.eng.token_logprobs else res
         for r, f in zip(rows, saved):
             r.feed = f
         # the eager step does not run the graphs' publish node: keep last_tok
@@ -198,8 +181,7 @@ class STTPipeline:
             entries.append((r.pl_launched, False))
             r.pl_launched += 1
             r.pl_fl += 1
-        self.inflight.append(_Step(rows, len(rows), torch.from_numpy(np.asarray(out, np.int32)),
-                                   None, entries, lp))
+        self.inflight.append(_Step(rows, len(rows), res, None, entries))
         self.eng.stats["decode_steps"] += 1
         return True
 
@@ -209,8 +191,8 @@ class STTPipeline:
         t0 = time.perf_counter()
         if st.event is not None:
             st.event.synchronize()
-        nxt = st.out[: st.B].numpy().copy()
-        lps = st.lp[: st.B].numpy().copy() if st.lp is not None else None
+        res = eng.io.result(st.out, st.B) if st.event is not None else st.out
+        nxt, lps = res if eng.token_logprobs else (res, None)
         eng.stats["gpu_wait_s"] += time.perf_counter() - t0
         done = []
         for b, (r, (k, sp)) in enumerate(zip(st.rows, st.entries)):

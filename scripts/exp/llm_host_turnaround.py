@@ -1,7 +1,11 @@
 """Where the time between two LLM decode steps goes (Llama-3-8B, 8 sequences,
 no concurrent STT): back-to-back graph replays (GPU only) vs replay + result
 read-back per step vs the engine's full decode_step (grammar advance, step
-metadata, H2D copy, replay, read-back)."""
+metadata staged in the pinned ring, replay, result ring read). Replays go
+through ``eng.io`` (engine/step_io.py), so the host's step number stays in step
+with the device counter. A graph replayed on its own runs padding-only steps
+(``pad_step``: no sequence, no KV write - the staging rows must hold metadata
+in that graph's layout), so its time is the weight streaming's, not attention's."""
 import json
 import os
 import sys
@@ -57,51 +61,56 @@ out["step_ms_by_T"] = {k: [round(min(v), 2), round(sorted(v)[len(v) // 2], 2), l
 ts.sort()
 out["decode_step_ms_median"] = round(ts[len(ts) // 2] * 1e3, 3)
 out["decode_step_ms_p90"] = round(ts[int(len(ts) * 0.9)] * 1e3, 3)
+io = eng.io
+
+
+def pad_step(gg):
+    """Stage the metadata the capture warm-up ran (no sequence, KV slots and
+    token sources -1, every row's slot the trash slot) and launch ``gg``."""
+    hb = io.stage(gg)
+    for a in hb.values():
+        a.fill(0)
+    hb["slots"].fill(-1)
+    hb["src"].fill(-1)
+    hb["row_slot"].fill(io.trash)
+    return io.replay(gg)
+
+
 for key, gg in sorted(eng._graphs.items()):
     if key[0] != B or key[2] != 512:
         continue
-    for _ in range(3):
-        gg["graph"].replay()
+    for _ in range(3):          # both staging rows now hold this graph's layout
+        pad_step(gg)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(20):
-        gg["graph"].replay()
+        io.replay(gg)
     torch.cuda.synchronize()
     out[f"replay_T{key[1]}_ms"] = round((time.perf_counter() - t0) / 20 * 1e3, 3)
 g = next(v for k, v in eng._graphs.items() if k[0] == B and k[1] == 16)
 # back-to-back replays (GPU time per step, no host turnaround)
 for _ in range(3):
-    g["graph"].replay()
+    pad_step(g)
 torch.cuda.synchronize()
 t0 = time.perf_counter()
 for _ in range(30):
-    g["graph"].replay()
+    io.replay(g)
 torch.cuda.synchronize()
 out["replay_back_to_back_ms"] = round((time.perf_counter() - t0) / 30 * 1e3, 3)
-# replay + read-back each step
+# replay + result ring read each step (the publish node wrote the ring)
 ts = []
 for _ in range(30):
     t0 = time.perf_counter()
-    g["graph"].replay()
-    g["out"][:B].cpu()
+    rslot = io.replay(g)
+    torch.cuda.current_stream().synchronize()
+    io.result(rslot, B)
     ts.append(time.perf_counter() - t0)
 ts.sort()
 out["replay_plus_readback_ms"] = round(ts[len(ts) // 2] * 1e3, 3)
-# replay + H2D metadata copies + read-back
-ts = []
-for _ in range(30):
-    t0 = time.perf_counter()
-    g["d32"].copy_(g["h32"], non_blocking=True)
-    g["d64"].copy_(g["h64"], non_blocking=True)
-    g["graph"].replay()
-    g["out"][:B].cpu()
-    ts.append(time.perf_counter() - t0)
-ts.sort()
-out["h2d_replay_readback_ms"] = round(ts[len(ts) // 2] * 1e3, 3)
 # CPU cost of the replay call itself
 torch.cuda.synchronize()
 t0 = time.perf_counter()
-g["graph"].replay()
+io.replay(g)
 out["replay_call_cpu_us"] = round((time.perf_counter() - t0) * 1e6, 1)
 torch.cuda.synchronize()
 out["stats"] = {k: (round(v, 4) if isinstance(v, float) else v) for k, v in eng.stats.items()}
