@@ -651,6 +651,229 @@ extern "C" int loqa_masked_argmax_lse(const void* logits, int is_bf16, long long
   return (int)hipGetLastError();
 }
 
+// ------------------------- masked argmax + log-probability + one probed column
+// loqa_masked_argmax_lse_probe: out_idx[b] and out_logprob[b] exactly as
+// loqa_masked_argmax_lse (the same masked (best, m, s) arithmetic in the same
+// order, the same chunk-record merge order: bit for bit), plus
+// out_probe[b] = x[b, probe[b]] - logsumexp(x[b, 0..V-1] over ALL columns, the
+// mask ignored): the log-softmax of one fixed column before the mask (Whisper's
+// log no_speech_prob at the start-of-transcript row).
+// A probing row keeps a second running (m, s) over all columns in the same
+// pass: each logit is still loaded once, the mask bits only decide whether a
+// term joins the first pair too. The thread whose vector group holds column
+// probe[b] keeps that logit; every other thread holds -inf for it, so a maximum
+// over the row's threads and chunk records moves it to the finalizing thread
+// unchanged. The result is (x[p] - m) - logf(s): -inf for a probed logit of
+// -inf or a row of -inf only (never NaN).
+// A row with probe[b] < 0 or >= V writes +0.0f and skips the second sum; the
+// branch is per row (blockIdx.y), so it is wave-uniform.
+// No memset, no atomics, bitwise repeatable, as the sibling.
+struct ArgLseProbe {
+  unsigned long long best;
+  float m, s;       // allowed columns
+  float am, as;     // all columns (probing rows)
+  float px, pad;    // the probed logit, -inf where this record does not hold it
+};
+
+__device__ __forceinline__ float lse_probe_logprob(bool probing, float px, float am, float as) {
+  if (!probing) return 0.f;
+  if (am == -INFINITY) return -INFINITY;      // every logit -inf (px too)
+  return (px - am) - logf(as);                // px == -inf: -inf; as >= 1
+}
+
+template <bool BF16, bool SINGLE>
+__global__ __launch_bounds__(ARG_THREADS) void masked_argmax_lse_probe_kernel(
+    const void* __restrict__ logits, long long ld, int V, const uint32_t* __restrict__ mask,
+    const int* __restrict__ mask_rows, int W, const int* __restrict__ probe,
+    ArgLseProbe* __restrict__ part, const int* __restrict__ token_ids, int* __restrict__ out_idx,
+    float* __restrict__ out_logprob, float* __restrict__ out_probe) {
+  __shared__ ArgLseProbe sred[ARG_THREADS / 64];
+  const int b = blockIdx.y;
+  const int v_begin = blockIdx.x * ARG_CHUNK;
+  const int v_end = min(V, v_begin + ARG_CHUNK);
+  const uint32_t* m = nullptr;
+  if (mask) m = mask + (size_t)(mask_rows ? mask_rows[b] : b) * W;
+  const int pb = probe[b];
+  const bool probing = pb >= 0 && pb < V;
+  unsigned long long best = 0;
+  float mx = -INFINITY, sum = 0.f;
+  float amx = -INFINITY, asum = 0.f, px = -INFINITY;
+  if (BF16) {
+    const bf16_t* row = reinterpret_cast<const bf16_t*>(logits) + (size_t)b * ld;
+    for (int v0 = v_begin + threadIdx.x * 8; v0 < v_end; v0 += ARG_THREADS * 8) {
+      if (v0 + 8 <= v_end && (ld % 8 == 0)) {
+        float f[8];
+        unpack8(*reinterpret_cast<const uint4*>(row + v0), f);
+        const uint32_t bits = m ? (m[v0 >> 5] >> (v0 & 31)) & 0xffu : 0xffu;
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          if ((bits >> j) & 1u) best = max(best, argpack(f[j], v0 + j));
+        lse_add_group<8>(mx, sum, f, bits);
+        if (probing) {
+          lse_add_group<8>(amx, asum, f, 0xffu);
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            if (v0 + j == pb) px = f[j];
+        }
+      } else {
+        for (int v = v0; v < min(v_end, v0 + 8); ++v) {
+          const bool ok = !m || ((m[v >> 5] >> (v & 31)) & 1u);
+          if (!ok && !probing) continue;
+          const float x = bf2f(row[v]);
+          if (ok) {
+            best = max(best, argpack(x, v));
+            lse_add(mx, sum, x);
+          }
+          if (probing) {
+            lse_add(amx, asum, x);
+            if (v == pb) px = x;
+          }
+        }
+      }
+    }
+  } else {
+    const float* row = reinterpret_cast<const float*>(logits) + (size_t)b * ld;
+    for (int v0 = v_begin + threadIdx.x * 4; v0 < v_end; v0 += ARG_THREADS * 4) {
+      if (v0 + 4 <= v_end && (ld % 4 == 0)) {
+        const float4 f4 = *reinterpret_cast<const float4*>(row + v0);
+        const float f[4] = {f4.x, f4.y, f4.z, f4.w};
+        const uint32_t bits = m ? (m[v0 >> 5] >> (v0 & 31)) & 0xfu : 0xfu;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if ((bits >> j) & 1u) best = max(best, argpack(f[j], v0 + j));
+        lse_add_group<4>(mx, sum, f, bits);
+        if (probing) {
+          lse_add_group<4>(amx, asum, f, 0xfu);
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (v0 + j == pb) px = f[j];
+        }
+      } else {
+        for (int v = v0; v < min(v_end, v0 + 4); ++v) {
+          const bool ok = !m || ((m[v >> 5] >> (v & 31)) & 1u);
+          if (!ok && !probing) continue;
+          const float x = row[v];
+          if (ok) {
+            best = max(best, argpack(x, v));
+            lse_add(mx, sum, x);
+          }
+          if (probing) {
+            lse_add(amx, asum, x);
+            if (v == pb) px = x;
+          }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long other = __shfl_xor(best, o, 64);
+    best = max(best, other);
+    const float m2 = __shfl_xor(mx, o, 64), s2 = __shfl_xor(sum, o, 64);
+    lse_merge(mx, sum, m2, s2);
+    if (probing) {
+      const float am2 = __shfl_xor(amx, o, 64), as2 = __shfl_xor(asum, o, 64);
+      lse_merge(amx, asum, am2, as2);
+      px = fmaxf(px, __shfl_xor(px, o, 64));
+    }
+  }
+  if ((threadIdx.x & 63) == 0)
+    sred[threadIdx.x >> 6] = ArgLseProbe{best, mx, sum, amx, asum, px, 0.f};
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int i = 1; i < ARG_THREADS / 64; ++i) {
+      best = max(best, sred[i].best);
+      lse_merge(mx, sum, sred[i].m, sred[i].s);
+      if (probing) {
+        lse_merge(amx, asum, sred[i].am, sred[i].as);
+        px = fmaxf(px, sred[i].px);
+      }
+    }
+    if (SINGLE) {
+      out_idx[b] = argunpack(best, token_ids);
+      out_logprob[b] = lse_logprob(best, mx, sum);
+      out_probe[b] = lse_probe_logprob(probing, px, amx, asum);
+    } else {
+      part[(size_t)b * gridDim.x + blockIdx.x] = ArgLseProbe{best, mx, sum, amx, asum, px, 0.f};
+    }
+  }
+}
+
+// one thread per row: the row's chunk records, merged in chunk order
+__global__ void argmax_lse_probe_finalize_kernel(const ArgLseProbe* __restrict__ part, int B,
+                                                 int chunks, int V, const int* __restrict__ probe,
+                                                 const int* __restrict__ token_ids,
+                                                 int* __restrict__ out_idx,
+                                                 float* __restrict__ out_logprob,
+                                                 float* __restrict__ out_probe) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const ArgLseProbe* p = part + (size_t)b * chunks;
+  const int pb = probe[b];
+  const bool probing = pb >= 0 && pb < V;
+  unsigned long long best = p[0].best;
+  float mx = p[0].m, sum = p[0].s;
+  float amx = p[0].am, asum = p[0].as, px = p[0].px;
+  for (int c = 1; c < chunks; ++c) {
+    best = max(best, p[c].best);
+    lse_merge(mx, sum, p[c].m, p[c].s);
+    if (probing) {
+      lse_merge(amx, asum, p[c].am, p[c].as);
+      px = fmaxf(px, p[c].px);
+    }
+  }
+  out_idx[b] = argunpack(best, token_ids);
+  out_logprob[b] = lse_logprob(best, mx, sum);
+  out_probe[b] = lse_probe_logprob(probing, px, amx, asum);
+}
+
+template <bool SINGLE>
+static void launch_masked_argmax_lse_probe(int is_bf16, dim3 grid, hipStream_t s,
+                                           const void* logits, long long ld, int V,
+                                           const uint32_t* mask, const int* mask_rows, int W,
+                                           const int* probe, ArgLseProbe* part,
+                                           const int* token_ids, int* out_idx, float* out_logprob,
+                                           float* out_probe) {
+  if (is_bf16)
+    hipLaunchKernelGGL((masked_argmax_lse_probe_kernel<true, SINGLE>), grid, dim3(ARG_THREADS), 0,
+                       s, logits, ld, V, mask, mask_rows, W, probe, part, token_ids, out_idx,
+                       out_logprob, out_probe);
+  else
+    hipLaunchKernelGGL((masked_argmax_lse_probe_kernel<false, SINGLE>), grid, dim3(ARG_THREADS), 0,
+                       s, logits, ld, V, mask, mask_rows, W, probe, part, token_ids, out_idx,
+                       out_logprob, out_probe);
+}
+
+// probe: int32 [B] (device); workspace: >= B * ceil(V / ARG_CHUNK) * 32 bytes
+// (device, 8-byte aligned); only touched when V > ARG_CHUNK, and needs no
+// initialisation.
+extern "C" int loqa_masked_argmax_lse_probe(const void* logits, int is_bf16, long long ld, int B,
+                                            int V, const uint32_t* mask, const int* mask_rows,
+                                            int W, const int* probe, int* out_idx,
+                                            float* out_logprob, float* out_probe, void* workspace,
+                                            const int* token_ids, hipStream_t s) {
+  if (B <= 0) return 0;
+  if (V <= 0 || ld < V || (mask && W * 32 < V) || !probe || !out_idx || !out_logprob || !out_probe)
+    return (int)hipErrorInvalidValue;
+  if (V <= ARG_CHUNK) {
+    launch_masked_argmax_lse_probe<true>(is_bf16, dim3(1, B), s, logits, ld, V, mask, mask_rows, W,
+                                         probe, nullptr, token_ids, out_idx, out_logprob,
+                                         out_probe);
+    return (int)hipGetLastError();
+  }
+  if (!workspace) return (int)hipErrorInvalidValue;
+  const int chunks = (V + ARG_CHUNK - 1) / ARG_CHUNK;
+  launch_masked_argmax_lse_probe<false>(is_bf16, dim3(chunks, B), s, logits, ld, V, mask,
+                                        mask_rows, W, probe, (ArgLseProbe*)workspace, token_ids,
+                                        out_idx, out_logprob, out_probe);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(argmax_lse_probe_finalize_kernel, dim3((B + 63) / 64), dim3(64), 0, s,
+                     (const ArgLseProbe*)workspace, B, chunks, V, probe, token_ids, out_idx,
+                     out_logprob, out_probe);
+  return (int)hipGetLastError();
+}
+
 // ------------------------------------------------- pipelined decode: step I/O
 // A decode step graph exchanges its host data without copy-engine operations
 // between graphs (each H2D / D2H copy on the decode stream cost a copy-engine
@@ -729,6 +952,30 @@ __global__ __launch_bounds__(256) void step_publish_lp_kernel(
   }
 }
 
+// step_publish_lp_kernel with two f32 values per sequence: slot (ctr % nres) of
+// the f32 ring is a row of two planes, lp[i] at [i] and lp2[i] at [plane + i],
+// both written before the fence and the counter store.
+__global__ __launch_bounds__(256) void step_publish_lp2_kernel(
+    const int* __restrict__ out, const float* __restrict__ lp, const float* __restrict__ lp2, int n,
+    int* __restrict__ res, int stride, float* __restrict__ res_lp, int lp_stride, int plane,
+    int nres, int* __restrict__ ctr, const int* __restrict__ row_slot, int* __restrict__ last_tok) {
+  const int c = ctr[0];
+  int* dst = res + (size_t)(c % nres) * stride;
+  float* dst_lp = res_lp + (size_t)(c % nres) * lp_stride;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const int v = out[i];
+    dst[i] = v;
+    dst_lp[i] = lp[i];
+    dst_lp[plane + i] = lp2[i];
+    last_tok[row_slot[i]] = v;     // padding rows write the trash slot
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __threadfence_system();
+    __hip_atomic_store(ctr, (c + 1) % (2 * nres), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
 // T: token rows at the head of the staged int32 block; src_off: offset of the
 // per-token source-slot array in it (see LLMEngine._decode_graph).
 extern "C" int loqa_step_fetch(void* d32, const void* h32, int n32, int stride32, void* d64,
@@ -759,6 +1006,19 @@ extern "C" int loqa_step_publish_lp(const int* out, const float* lp, int n, void
     return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(step_publish_lp_kernel, dim3(1), dim3(256), 0, s, out, lp, n, (int*)res, stride,
                      (float*)res_lp, lp_stride, nres, ctr, row_slot, last_tok);
+  return (int)hipGetLastError();
+}
+
+// res_lp rows: lp_stride floats, lp at [0, n), lp2 at [plane, plane + n)
+extern "C" int loqa_step_publish_lp2(const int* out, const float* lp, const float* lp2, int n,
+                                     void* res, int stride, void* res_lp, int lp_stride, int plane,
+                                     int nres, int* ctr, const int* row_slot, int* last_tok,
+                                     hipStream_t s) {
+  if (n < 0 || n > stride || n > plane || plane > lp_stride - n || nres < 1 || !lp || !lp2 ||
+      !res_lp)
+    return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(step_publish_lp2_kernel, dim3(1), dim3(256), 0, s, out, lp, lp2, n, (int*)res,
+                     stride, (float*)res_lp, lp_stride, plane, nres, ctr, row_slot, last_tok);
   return (int)hipGetLastError();
 }
 

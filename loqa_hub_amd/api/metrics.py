@@ -55,6 +55,10 @@ class MetricsHandler:
                 out.append(_line("loqa_llm_weight_dtype", 1,
                                  {"dtype": getattr(lw, "weight_dtype", "bf16")}))
             for k, v in pipe.stt.stats.items():
+                if isinstance(v, dict):     # utterances per detected language
+                    for lab, n in sorted(v.items()):
+                        out.append(_line("loqa_stt_" + k, n, {"language": lab}))
+                    continue
                 out.append(_line("loqa_stt_" + k, v))
         from ..utils.tracing import tracer
         for stage, st in tracer().summary().items():

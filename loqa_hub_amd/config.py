@@ -215,6 +215,16 @@ class GPUConfig:
     # backend); below stt_confirm_below the hub asks the user to confirm
     stt_confidence: str = "heuristic"
     stt_confirm_below: float = 0.6
+    # STT_LANGUAGE=auto (or set and empty): candidate languages of the gpu
+    # backend's detection ([] = every language the tokenizer has)
+    stt_languages: list = field(default_factory=list)
+    # Whisper's no-speech rule on the gpu backend: a 30 s window whose
+    # no_speech_prob > stt_no_speech_threshold and whose mean token
+    # log-probability < stt_logprob_threshold gives no text (the reference's
+    # STT service answers such a segment with an empty transcript)
+    stt_no_speech: str = "off"        # off | on
+    stt_no_speech_threshold: float = 0.6
+    stt_logprob_threshold: float = -1.0
     # relay audio: "fixed" (every chunk is 16 kHz, AudioChunk.sample_rate is
     # ignored: the reference's behaviour) or "relay" (the stream's own rate, one
     # of AUDIO_SAMPLE_RATES; the gpu STT resamples it to 16 kHz on the device,
@@ -352,6 +362,20 @@ class Config:
         if not 0.0 <= self.gpu.stt_confirm_below <= 1.0:
             raise ConfigError("HUB_STT_CONFIRM_BELOW must be in [0, 1]: "
                               f"{self.gpu.stt_confirm_below}")
+        if self.gpu.stt_no_speech not in ("off", "on"):
+            raise ConfigError(f"invalid HUB_STT_NO_SPEECH (off | on): {self.gpu.stt_no_speech}")
+        if self.gpu.stt_no_speech == "on" and self.gpu.stt_backend != "gpu":
+            raise ConfigError("HUB_STT_NO_SPEECH=on needs HUB_STT_BACKEND=gpu: "
+                              f"{self.gpu.stt_backend}")
+        if not 0.0 < self.gpu.stt_no_speech_threshold <= 1.0:
+            raise ConfigError("HUB_STT_NO_SPEECH_THRESHOLD must be in (0, 1]: "
+                              f"{self.gpu.stt_no_speech_threshold}")
+        if not self.gpu.stt_logprob_threshold <= 0.0:
+            raise ConfigError("HUB_STT_LOGPROB_THRESHOLD must be <= 0: "
+                              f"{self.gpu.stt_logprob_threshold}")
+        for c in self.gpu.stt_languages:
+            if not re.fullmatch(r"[a-z]{2,3}", c):
+                raise ConfigError(f"invalid HUB_STT_LANGUAGES entry: {c!r}")
 
 
 def parse_relay_groups(s: str) -> dict:
@@ -378,6 +402,27 @@ def _tts_sample_rate(e) -> int:
         raise ConfigError(f"invalid configuration: invalid HUB_TTS_SAMPLE_RATE: {v}") from None
 
 
+def _stt_language(e) -> str:
+    """``STT_LANGUAGE``: unset = "en"; "auto", or set and empty (the reference
+    passes an empty language through, and a Whisper service then detects it) =
+    "auto"."""
+    v = e.get("STT_LANGUAGE")
+    if v is None:
+        return "en"
+    v = str(v).strip()
+    return "auto" if v == "" or v.lower() == "auto" else v
+
+
+def _strict_float(e, default: float, key: str) -> float:
+    v = env_str(e, "", key).strip()
+    if v == "":
+        return default
+    try:
+        return float(v)
+    except ValueError:
+        raise ConfigError(f"invalid configuration: invalid {key}: {v}") from None
+
+
 def load(env=None) -> Config:
     """Build the configuration from ``env`` (default ``os.environ``) and
     validate it; raises ``ConfigError`` ("invalid configuration: ...")."""
@@ -393,7 +438,7 @@ def load(env=None) -> Config:
         ),
         stt=STTConfig(
             url=env_str(e, "http://stt:8000", "STT_URL"),
-            language=env_str(e, "en", "STT_LANGUAGE"),
+            language=_stt_language(e),
             temperature=env_float(e, 0.0, "STT_TEMPERATURE"),
             max_tokens=env_int(e, 224, "STT_MAX_TOKENS"),
         ),
@@ -456,6 +501,11 @@ def load(env=None) -> Config:
             stt_backend=env_str(e, "gpu", "HUB_STT_BACKEND"),
             stt_confidence=env_str(e, "heuristic", "HUB_STT_CONFIDENCE").lower(),
             stt_confirm_below=env_float(e, 0.6, "HUB_STT_CONFIRM_BELOW"),
+            stt_languages=[c.strip().lower() for c in
+                           env_str(e, "", "HUB_STT_LANGUAGES").split(",") if c.strip()],
+            stt_no_speech=env_str(e, "off", "HUB_STT_NO_SPEECH").strip().lower(),
+            stt_no_speech_threshold=_strict_float(e, 0.6, "HUB_STT_NO_SPEECH_THRESHOLD"),
+            stt_logprob_threshold=_strict_float(e, -1.0, "HUB_STT_LOGPROB_THRESHOLD"),
             audio_input_rate=env_str(e, "fixed", "HUB_AUDIO_INPUT_RATE").lower(),
             tts_sample_rate=_tts_sample_rate(e),
             tts_backend=env_str(e, "gpu", "HUB_TTS_BACKEND"),

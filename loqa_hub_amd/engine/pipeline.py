@@ -53,6 +53,7 @@ class PipelineJob:
     queue: ExecutionResult | None = None
     error: str = ""
     stt_failed: bool = False
+    no_speech: bool = False                 # every window fell to the STT engine's no-speech rule
     llm_steps: int = 0                      # decode steps the intent parse sampled in
     t: dict = field(default_factory=dict)   # stage timestamps (perf_counter)
 
@@ -76,10 +77,16 @@ class VoicePipeline:
                  continuous: bool | None = None, batch_window: float = 0.002,
                  max_batch: int = 8, stt_priority: int = -1,
                  stt_continuous: bool | None = None,
-                 stt_confirm_below: float = CONFIRMATION_THRESHOLD):
+                 stt_confirm_below: float = CONFIRMATION_THRESHOLD,
+                 stt_acoustic: bool | None = None):
         self.stt, self.llm, self.nats = stt, llm, nats
         # confirmation threshold of the transcript's confidence (HUB_STT_CONFIRM_BELOW)
         self.stt_confirm_below = stt_confirm_below
+        # the confidence comes from the engine's avg_logprob (HUB_STT_CONFIDENCE=
+        # acoustic); None: whenever the engine records one. False keeps the text
+        # heuristic with an engine that records log-probabilities for its
+        # no-speech rule only
+        self.stt_acoustic = stt_acoustic
         self.min_response_tokens = min_response_tokens
         self.queue_max_duration = queue_max_duration
         self.rollback = rollback
@@ -135,7 +142,12 @@ class VoicePipeline:
             j.stt_failed, j.error = True, "stt: injected fault"
             return
         # r.avg_logprob: None unless the STT engine records token log-probabilities
-        j.transcription = to_transcription_result(r.text, r.avg_logprob, self.stt_confirm_below)
+        # language / no_speech_prob: None unless it reads the start-of-transcript logits
+        j.transcription = to_transcription_result(
+            r.text, r.avg_logprob if self.stt_acoustic is not False else None,
+            self.stt_confirm_below, language=r.language,
+            language_prob=r.language_prob, no_speech_prob=r.no_speech_prob)
+        j.no_speech = r.gated_windows > 0 and r.gated_windows == r.windows
 
     def build_request(self, j: PipelineJob) -> GenRequest | None:
         if j.stt_failed:

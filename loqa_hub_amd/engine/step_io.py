@@ -2,7 +2,7 @@
 
 A decode-step graph exchanges its host data without copy-engine operations
 (csrc/kernels/elementwise.hip, "pipelined decode: step I/O"): every graph is
-``loqa_step_fetch`` -> step body -> ``loqa_step_publish[_lp]``.
+``loqa_step_fetch`` -> step body -> ``loqa_step_publish[_lp[2]]``.
 
 * The host stages a step's metadata in a pinned ring of ``STAGE_SLOTS`` rows;
   the fetch node reads the row of this launch into the graph's device buffers
@@ -79,18 +79,28 @@ class StepIO:
     WRAP = 2 * RES_SLOTS    # both counters wrap here, as step_publish_kernel wraps *ctr
     WIDTH = 256         # result ring row: the most sequences (B_pad) of one step
 
-    def __init__(self, device, largest: StepLayout, last_tok: torch.Tensor, logprobs: bool = False):
+    def __init__(self, device, largest: StepLayout, last_tok: torch.Tensor,
+                 logprobs: bool | int = False):
         """``largest``: the layout of the engine's largest bucket (sizes the
         staging rows); ``last_tok``: the engine's last-token table, its last
-        entry the trash slot; ``logprobs``: an f32 result ring beside the tokens'."""
+        entry the trash slot; ``logprobs``: an f32 result ring beside the
+        tokens'; ``2``: its rows carry two f32 values per sequence (the token's
+        log-probability and a probed one), as two planes of ``WIDTH``."""
+        if logprobs not in (False, True, 2):
+            raise ValueError("logprobs: False, True or 2")
+        self.lp_cols = int(logprobs)
         self.device = device
         self.n32, self.n64 = largest.n32, largest.n64
         self.last_tok, self.trash = last_tok, last_tok.numel() - 1
-        self.stage32 = torch.zeros(self.STAGE_SLOTS, self.n32, dtype=torch.int32).pin_memory()
-        self.stage64 = torch.zeros(self.STAGE_SLOTS, self.n64, dtype=torch.int64).pin_memory()
-        self.res = torch.zeros(self.RES_SLOTS, self.WIDTH, dtype=torch.int32).pin_memory()
-        self.res_lp = torch.zeros(self.RES_SLOTS, self.WIDTH, dtype=torch.float32).pin_memory() \
-            if logprobs else None
+        # pinned for the device's zero-copy reads and writes (a host-only StepIO,
+        # device "cpu", keeps plain memory: its rings and result() work the same)
+        pin = (lambda t: t.pin_memory()) if torch.device(device).type == "cuda" else (lambda t: t)
+        self.stage32 = pin(torch.zeros(self.STAGE_SLOTS, self.n32, dtype=torch.int32))
+        self.stage64 = pin(torch.zeros(self.STAGE_SLOTS, self.n64, dtype=torch.int64))
+        self.res = pin(torch.zeros(self.RES_SLOTS, self.WIDTH, dtype=torch.int32))
+        lp_shape = (self.RES_SLOTS, self.WIDTH) if self.lp_cols < 2 else \
+            (self.RES_SLOTS, 2, self.WIDTH)
+        self.res_lp = pin(torch.zeros(lp_shape, dtype=torch.float32)) if logprobs else None
         self.ctr = torch.zeros(1, dtype=torch.int32, device=device)   # launched step graphs
         self.step_no = 0                                              # the host's copy of it
         self._res = self.res.numpy()
@@ -105,6 +115,7 @@ class StepIO:
     def capture(self, layout: StepLayout, T_pad: int, body, warm=None) -> dict:
         """One decode-step graph: fetch node, ``body(dev)`` (the sampled tokens
         of the first ``B_pad`` rows; with the log-prob ring ``(tokens,
+        logprobs)``, with its two-value rows ``(tokens, logprobs, probe
         logprobs)``), publish node. ``dev`` are the graph's device buffers in
         ``layout``. ``warm(dev)``: what the warm-up runs instead of the body."""
         B_pad = layout.shapes["row_slot"][0]
@@ -136,7 +147,13 @@ class StepIO:
                 self.stage64.data_ptr(), layout.n64, self.n64, lib.ptr(self.ctr), T_pad,
                 layout.src_off, lib.ptr(self.last_tok), st), "step_fetch")
             out = body(dev)
-            if self.res_lp is not None:
+            if self.lp_cols == 2:
+                lib.check(k.loqa_step_publish_lp2(
+                    lib.ptr(out[0]), lib.ptr(out[1]), lib.ptr(out[2]), B_pad, self.res.data_ptr(),
+                    self.WIDTH, self.res_lp.data_ptr(), 2 * self.WIDTH, self.WIDTH, self.RES_SLOTS,
+                    lib.ptr(self.ctr), lib.ptr(dev["row_slot"]), lib.ptr(self.last_tok), st),
+                    "step_publish_lp2")
+            elif self.res_lp is not None:
                 lib.check(k.loqa_step_publish_lp(
                     lib.ptr(out[0]), lib.ptr(out[1]), B_pad, self.res.data_ptr(), self.WIDTH,
                     self.res_lp.data_ptr(), self.WIDTH, self.RES_SLOTS, lib.ptr(self.ctr),
@@ -168,10 +185,13 @@ class StepIO:
 
     def result(self, rslot: int, B: int):
         """Copies of the first ``B`` tokens of result row ``rslot`` (once its
-        step has finished); with the log-prob ring ``(tokens, logprobs)``."""
+        step has finished); with the log-prob ring ``(tokens, logprobs)``, with
+        its two-value rows ``(tokens, logprobs, probe logprobs)``."""
         toks = self._res[rslot, :B].copy()
         if self._res_lp is None:
             return toks
+        if self.lp_cols == 2:
+            return toks, self._res_lp[rslot, 0, :B].copy(), self._res_lp[rslot, 1, :B].copy()
         return toks, self._res_lp[rslot, :B].copy()
 
 

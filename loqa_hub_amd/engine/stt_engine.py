@@ -29,7 +29,7 @@ from ..utils.tracing import tracer
 from .batching import join_futures, plan_step
 from .kv_cache import PagedKVCache
 from .step_io import StepIO, StepLayout, decode_buckets, fill_meta, step_shapes, to_device
-from .tokenizer import get_tokenizer
+from .tokenizer import SyntheticTokenizer, SyntheticWhisperTokenizer, get_tokenizer
 
 log = logging.getLogger("loqa.stt")
 
@@ -81,6 +81,14 @@ class STTRequest:
     # Teacher-forced requests emit their target, not the sample: empty / None.
     logprobs: list[float] = field(default_factory=list)
     avg_logprob: float | None = None
+    # STTEngine(sot_probe=True): the language read from the start-of-transcript
+    # logits (code; with a fixed language that one) and its probability among
+    # the candidate languages, Whisper's no_speech_prob of every 30 s window and
+    # their minimum (the utterance is silent only if every window is)
+    language: str | None = None
+    language_prob: float | None = None
+    no_speech_probs: list[float] = field(default_factory=list)
+    no_speech_prob: float | None = None
     seq_id: int = -1
     t_done: float = 0.0
     t_enc0: float = 0.0               # encoder start / end, decoder start (perf_counter)
@@ -100,6 +108,13 @@ class STTRequest:
     win_texts: list = field(default_factory=list)
     prev_tokens: list = field(default_factory=list)
     prompt_steps: int = 1
+    # the window's prompt as the feeds of its first ``prompt_steps`` steps (a
+    # probing engine appends the last one when the SOT step has retired)
+    chunks: list = field(default_factory=list)
+    sot_step: int = -1                # probing engine: the step whose feed ends in SOT
+    sot_pending: bool = False         # ... and its result has not been read yet
+    lang_id: int = -1                 # the language token fed after SOT
+    gated_windows: int = 0            # windows dropped by the no-speech rule
     lp_sum: float = 0.0               # finished windows' log-probability sum / count
     lp_n: int = 0
 
@@ -120,10 +135,28 @@ class STTEngine:
                  block_size: int = 16, use_graphs: bool = True, fast_decode: bool = True,
                  fused: bool = True, weights: WhisperWeights | None = None,
                  contended_tuning: bool = False, tokenizer=None, language: str = "en",
-                 token_logprobs: bool = False):
+                 token_logprobs: bool = False, sot_probe: bool = False,
+                 languages: list[str] | None = None, no_speech: bool = False,
+                 no_speech_threshold: float = 0.6, logprob_threshold: float = -1.0):
         self.cfg = cfg
+        # language "auto" (or empty, as the reference passes an empty
+        # STT_LANGUAGE through): the language is the argmax over the candidate
+        # language tokens at the start-of-transcript position
+        language = (language or "auto").strip().lower() or "auto"
+        self.auto_language = language == "auto"
+        # no_speech: Whisper's rule drops a freely decoded window whose
+        # no_speech_prob > no_speech_threshold and whose mean token
+        # log-probability < logprob_threshold
+        self.no_speech = bool(no_speech)
+        self.no_speech_threshold = float(no_speech_threshold)
+        self.logprob_threshold = float(logprob_threshold)
+        # the decoder reads the start-of-transcript logits (language and
+        # no_speech_prob): SOT ends a step of its own, every step samples through
+        # ops.masked_argmax_logprob_probe
+        self.sot_probe = bool(sot_probe) or self.auto_language or self.no_speech
         # every step also returns the log-softmax (after the suppress mask) of
         # the token it samples (ops.masked_argmax_logprob); off: ops.masked_argmax
+        token_logprobs = bool(token_logprobs) or self.sot_probe
         self.token_logprobs = token_logprobs
         self.device = torch.device(device)
         if self.device.type == "cuda" and self.device.index is None:
@@ -138,6 +171,14 @@ class STTEngine:
         self.weights.max_wgs = self.max_wgs or ops.MAX_DECODE_WGS
         self.model = WhisperModel(self.weights)
         self.tok = tokenizer or get_tokenizer(cfg.vocab_size)
+        if self.sot_probe and isinstance(self.tok, SyntheticTokenizer):
+            self.tok = SyntheticWhisperTokenizer(self.tok)
+        self.step_fields = self.STEP_FIELDS
+        if self.sot_probe:
+            self._init_probe(language, languages)
+            language = self.lang_codes[0]      # placeholder in ``sot``: fed per request
+            i = self.STEP_FIELDS.index("src")
+            self.step_fields = self.STEP_FIELDS[:i] + ("mask_row", "probe") + self.STEP_FIELDS[i:]
         # start-of-transcript prompt; the language token follows STT_LANGUAGE
         # (the reference passes it to its STT service)
         try:
@@ -158,7 +199,17 @@ class STTEngine:
         # reference's STT service decodes); one packed mask row for every
         # sequence. The synthetic tokenizer of the random-init weights: none.
         self._sup = self._sup_rows = None
-        if hasattr(self.tok, "sampling_mask"):
+        if self.sot_probe:
+            # a table of two rows, picked per sequence by the step's ``mask_row``
+            # field: 0 = the suppress mask (all ones for the synthetic tokenizer),
+            # 1 = the candidate language tokens (the SOT step)
+            from ..ops.reference import pack_mask
+            row0 = self.tok.sampling_mask(keep=(self.eot,)) if hasattr(self.tok, "sampling_mask") \
+                else torch.ones(cfg.vocab_size, dtype=torch.bool)
+            row1 = torch.zeros(cfg.vocab_size, dtype=torch.bool)
+            row1[self.lang_ids] = True
+            self._sup = pack_mask(torch.stack([row0, row1])).to(self.device)
+        elif hasattr(self.tok, "sampling_mask"):
             from ..ops.reference import pack_mask
             self._sup = pack_mask(self.tok.sampling_mask(keep=(self.eot,))[None]).to(self.device)
             self._sup_rows = torch.zeros(max(256, 2 * max_batch), dtype=torch.int32,
@@ -176,6 +227,8 @@ class STTEngine:
                       "encode_s": 0.0}
         if token_logprobs:
             self.stats.update(logprob_tokens=0, logprob_sum=0.0)
+        if self.sot_probe:
+            self.stats.update(no_speech_windows=0, no_speech_utterances=0, languages={})
         self.max_batch = max_batch
         self.fast_decode = fast_decode
         # fused-epilogue decoder GEMMs (8 launches per layer) for Mpad <= 64
@@ -220,11 +273,48 @@ class STTEngine:
             # the tokens' log-probabilities are published beside them
             b_max = next((b for b in self.SEQ_BUCKETS if b >= max_batch), self.SEQ_BUCKETS[-1])
             self.last_tok = torch.zeros(max_batch + 1, dtype=torch.int32, device=self.device)
-            self.io = StepIO(self.device, self.step_layout(b_max, ops.MPADS[-1], self.max_blocks),
-                             self.last_tok, logprobs=token_logprobs)
+            self.io = StepIO(self.device, self._layout(b_max, ops.MPADS[-1]), self.last_tok,
+                             logprobs=2 if self.sot_probe else token_logprobs)
         # two decoder steps in flight (the host prepares step j+1 while step j
         # runs); LOQA_STT_PIPELINE=0: one synchronous step at a time
         self.pipelined = self.use_graphs and os.environ.get("LOQA_STT_PIPELINE", "1") != "0"
+
+    def _init_probe(self, language: str, languages: list[str] | None) -> None:
+        """Tokens of the start-of-transcript probe: ``nospeech`` and the
+        candidate languages (``lang_codes`` / ``lang_ids``, in token order; a
+        fixed language: that one alone)."""
+        tok = self.tok
+        self.nospeech = None
+        for name in ("<|nospeech|>", "<|nocaptions|>"):
+            try:
+                self.nospeech = tok.token_id(name)
+                break
+            except KeyError:
+                pass
+        if self.nospeech is None:
+            raise ValueError("STT start-of-transcript probe: the tokenizer has neither "
+                             "<|nospeech|> nor <|nocaptions|>")
+        known = tok.language_tokens() if hasattr(tok, "language_tokens") else {}
+        want = [language] if not self.auto_language else \
+            [str(c).strip().lower() for c in languages] if languages else list(known)
+        if not want:
+            raise ValueError("STT language detection: the tokenizer has no language tokens")
+        for c in want:
+            if c not in known:
+                raise ValueError(f"STT language {c!r}: no <|{c}|> token in the tokenizer "
+                                 "(a multilingual Whisper tokenizer.json has one)")
+        pairs = sorted({(known[c], c) for c in want})
+        self.lang_ids = [i for i, _ in pairs]
+        self.lang_codes = [c for _, c in pairs]
+        self._lang_code = dict(pairs)
+
+    def _layout(self, B_pad: int, T_pad: int) -> StepLayout:
+        """``step_layout`` of this engine (a probing one stages two more
+        per-sequence fields, ``mask_row`` and ``probe``)."""
+        if not self.sot_probe:
+            return self.step_layout(B_pad, T_pad, self.max_blocks)
+        return StepLayout(step_shapes(self.step_fields, B_pad, T_pad, self.max_blocks),
+                          max(16, ops.mpad_for(B_pad)))
 
     # ------------------------------------------------------------ front end
     def upload(self, reqs: list[STTRequest], device_pcm: torch.Tensor | None = None
@@ -379,10 +469,13 @@ class STTEngine:
         return self.xkv
 
     def _host_meta(self, live: list[STTRequest], B_pad: int, T_pad: int,
-                   out: dict | None = None, feeds: list | None = None) -> tuple[int, dict]:
+                   out: dict | None = None, feeds: list | None = None,
+                   sot: list | None = None) -> tuple[int, dict]:
         """Host metadata of one step feeding ``feeds`` (default: every
         request's ``feed``); ``out`` = preallocated views (a staging row) to
-        fill in place and return."""
+        fill in place and return. ``sot`` (probing engine): the requests whose
+        feed ends in SOT this step (default: ``sot_pending`` and the whole
+        remaining prompt fed)."""
         T_enc = self.cfg.n_audio_ctx
         if feeds is None:
             feeds = [r.feed for r in live]
@@ -397,6 +490,17 @@ class STTEngine:
         enc_starts[n:] = 0
         enc_lens[:n] = T_enc
         enc_lens[n:] = 0
+        if self.sot_probe:
+            if sot is None:
+                sot = [r.sot_pending and len(f) == len(r.feed) for r, f in zip(live, feeds)]
+            if out is None:
+                host["mask_row"] = np.zeros(B_pad, np.int32)
+                host["probe"] = np.zeros(B_pad, np.int32)
+            mask_row, probe = host["mask_row"], host["probe"]
+            mask_row[:n] = [1 if x else 0 for x in sot]
+            mask_row[n:] = 0
+            probe[:n] = [self.nospeech if x else -1 for x in sot]
+            probe[n:] = -1
         return max([len(f) for f in feeds] + [1]), host
 
     def _dev(self, host: dict, dst: dict | None = None) -> dict:
@@ -415,8 +519,20 @@ class STTEngine:
             return fn(logits)
         return fn(logits, self._sup, self._sup_rows[: logits.shape[0]])
 
+    def _sample(self, logits: torch.Tensor, dev: dict):
+        """``_argmax``; a probing engine: (tokens, log-probabilities, probed
+        log-probabilities) under each sequence's mask row, the probe read from
+        the step's ``probe`` field."""
+        if not self.sot_probe:
+            return self._argmax(logits)
+        B = logits.shape[0]
+        return ops.masked_argmax_logprob_probe(logits, self._sup, dev["mask_row"][:B],
+                                               dev["probe"][:B])
+
     def _host(self, res, B: int | None = None):
-        """A step's device result (``_argmax``) as numpy, cut to B rows."""
+        """A step's device result (``_sample``) as numpy, cut to B rows."""
+        if self.sot_probe:
+            return tuple(x[:B].cpu().numpy() for x in res)
         if self.token_logprobs:
             return res[0][:B].cpu().numpy(), res[1][:B].cpu().numpy()
         return res[:B].cpu().numpy()
@@ -429,13 +545,13 @@ class STTEngine:
                                        self.kv.k, self.kv.v, self.xkv, dev["enc_starts"],
                                        dev["enc_lens"], dev["logit_idx"], self.ws, self.scratch,
                                        ns, self.SPLIT_KEYS, self.cross_split_keys)
-            return self._argmax(logits[:B_pad, : self.cfg.vocab_size])
+            return self._sample(logits[:B_pad, : self.cfg.vocab_size], dev)
         logits = decode_step_fast(self.model, dev["tokens"], dev["positions"], dev["slots"],
                                   dev["cu_q"], dev["ctx_lens"], dev["block_tables"], max_q,
                                   self.kv.k, self.kv.v, self.xkv, dev["enc_starts"],
                                   dev["enc_lens"], dev["logit_idx"], self.ws, ns,
                                   self.SPLIT_KEYS)
-        return self._argmax(logits[:B_pad, : self.cfg.vocab_size])
+        return self._sample(logits[:B_pad, : self.cfg.vocab_size], dev)
 
     def _graph(self, B_pad: int, T_pad: int, ctx: int) -> dict:
         """Captured decode step for (sequence bucket, token bucket, context
@@ -449,7 +565,7 @@ class STTEngine:
         if g is None:
             max_q = max(1, min(len(self.sot), T_pad))
             g = self._graphs[key] = self.io.capture(
-                self.step_layout(B_pad, T_pad, self.max_blocks), T_pad,
+                self._layout(B_pad, T_pad), T_pad,
                 lambda dev: self._fast_forward(dev, max_q, B_pad, ctx))
         return g
 
@@ -510,9 +626,11 @@ class STTEngine:
         self._graphs_frozen = True
         return n + len(buckets)
 
-    def _step(self, live: list[STTRequest]):
+    def _step(self, live: list[STTRequest], sot: list | None = None):
         """One decoder step for every live request (its ``feed`` tokens): the
-        sampled tokens, with ``token_logprobs`` (tokens, log-probabilities)."""
+        sampled tokens, with ``token_logprobs`` (tokens, log-probabilities), a
+        probing engine (tokens, log-probabilities, probed log-probabilities).
+        ``sot``: see ``_host_meta``."""
         B = len(live)
         T = sum(len(r.feed) for r in live)
         if self.fast_decode:
@@ -524,7 +642,7 @@ class STTEngine:
                 t0 = time.perf_counter()
                 g = self._graph(B_pad, T_pad, C)
                 hb = self.io.stage(g)
-                self._host_meta(live, B_pad, T_pad, out=hb)
+                self._host_meta(live, B_pad, T_pad, out=hb, sot=sot)
                 hb["src"].fill(-1)
                 hb["row_slot"].fill(self.io.trash)
                 t1 = time.perf_counter()
@@ -534,11 +652,11 @@ class STTEngine:
                 self.stats["host_pre_s"] += t1 - t0
                 self.stats["gpu_wait_s"] += time.perf_counter() - t1
                 return out
-            max_q, host = self._host_meta(live, B_pad, T_pad)
+            max_q, host = self._host_meta(live, B_pad, T_pad, sot=sot)
             return self._host(self._fast_forward(self._dev(host), max_q, B_pad), B)
-        return self._eager_step(live)
+        return self._eager_step(live, sot) if self.sot_probe else self._eager_step(live)
 
-    def _eager_step(self, live: list[STTRequest]):
+    def _eager_step(self, live: list[STTRequest], sot: list | None = None):
         """Reference decode path (hipBLASLt GEMMs, eager launches)."""
         T_enc = self.cfg.n_audio_ctx
         toks, pos, slots, cu, ctx, lidx = [], [], [], [0], [], []
@@ -565,7 +683,13 @@ class STTEngine:
             dev(toks, torch.int32), dev(pos, torch.int32), dev(slots, torch.int32),
             dev(cu, torch.int32), dev(ctx, torch.int32), dev(bt, torch.int32), max_q, max_ctx,
             self.kv.k, self.kv.v, self.xkv, enc_starts, enc_lens, dev(lidx, torch.int64), self.ws)
-        return self._host(self._argmax(logits))
+        if not self.sot_probe:
+            return self._host(self._argmax(logits))
+        if sot is None:
+            sot = [r.sot_pending for r in live]
+        meta = {"mask_row": dev([1 if x else 0 for x in sot], torch.int32),
+                "probe": dev([self.nospeech if x else -1 for x in sot], torch.int32)}
+        return self._host(self._sample(logits, meta))
 
     # ----------------------------------------------------------- admission
     def _admit(self, reqs: list[STTRequest], slots: list[int],
@@ -623,6 +747,8 @@ class STTEngine:
             r.t_done = 0.0
             r.win_texts, r.prev_tokens = [], []
             r.lp_sum, r.lp_n, r.avg_logprob = 0.0, 0, None
+            r.language = r.language_prob = r.no_speech_prob = None
+            r.no_speech_probs, r.lang_id, r.gated_windows = [], -1, 0
             if not r.slots:
                 r.slots = [r.slot]
             self._begin_window(r, 0)
@@ -652,12 +778,48 @@ class STTEngine:
             prompt = [self.sop] + r.prev_tokens[-PREV_TOKENS:]
         r.tokens, r.step, r.feed = [], 0, prompt + list(self.sot)
         r.logprobs = []
-        r.prompt_steps = -(-len(r.feed) // len(self.sot))
+        c = len(self.sot)
+        r.sot_step, r.sot_pending = -1, False
+        if self.sot_probe:
+            # SOT is the last token of a step of its own; what follows it is
+            # fed once that step's logits are read (_sot_result)
+            r.feed = prompt + self.sot[:1]
+            r.chunks = self._prompt_chunks(r.feed)
+            r.sot_step, r.sot_pending = len(r.chunks) - 1, True
+            r.prompt_steps = len(r.chunks) + 1
+        else:
+            r.chunks = [r.feed[i:i + c] for i in range(0, len(r.feed), c)]
+            r.prompt_steps = len(r.chunks)
         r.target = None
         text = self._window_text(r, w)
         if text is not None:
-            room = self.cfg.n_text_ctx - 8 - len(r.feed)
+            room = self.cfg.n_text_ctx - 8 - len(prompt) - len(self.sot)
             r.target = self.tok.encode(" " + text.strip())[:room] + [self.eot]
+
+    def _prompt_chunks(self, prompt: list[int]) -> list[list[int]]:
+        """A prompt ending in SOT as step feeds of at most len(sot) tokens; SOT
+        ends the last one, so no feed crosses it."""
+        c = len(self.sot)
+        return [prompt[i:i + c] for i in range(0, len(prompt), c)]
+
+    def _sot_result(self, r: STTRequest, idx: int, lp: float, plp: float) -> list[int]:
+        """The SOT step of ``r``'s window has retired with (language token, its
+        log-probability among the candidates, log no_speech_prob): record them
+        and return the host-known feed that follows SOT. Later windows of an
+        utterance keep window 0's language."""
+        if r.win == 0 or r.lang_id < 0:
+            r.lang_id = int(idx)
+            r.language = self._lang_code.get(r.lang_id)
+            r.language_prob = float(np.exp(np.float64(lp)))
+            if r.language is None:
+                raise RuntimeError(f"STT language detection returned token {r.lang_id}")
+            counts = self.stats["languages"]
+            counts[r.language] = counts.get(r.language, 0) + 1
+        r.no_speech_probs.append(float(np.exp(np.float64(plp))))
+        r.sot_pending = False
+        post = [r.lang_id] + self.sot[2:]
+        r.chunks.append(post)
+        return post
 
     def _decode_once(self, live: list[STTRequest]) -> list[STTRequest]:
         """One decoder step over ``live`` (at most ``step_tokens`` tokens: a
@@ -672,15 +834,21 @@ class STTEngine:
                 rest.append(r.feed[n:])
                 r.feed = r.feed[:n]
         live = step
-        nxt = self._step(live)
-        lps = None
-        if self.token_logprobs:
+        nxt = self._step(live, [r.sot_pending and not x for r, x in zip(live, rest)]) \
+            if self.sot_probe else self._step(live)
+        lps = plps = None
+        if self.sot_probe:
+            nxt, lps, plps = nxt
+        elif self.token_logprobs:
             nxt, lps = nxt
         self.stats["decode_steps"] += 1
         done = []
         for j, r in enumerate(live):
             if rest[j]:            # part of the prompt still to feed: logits unused
                 r.feed = rest[j]
+                continue
+            if r.sot_pending:      # the SOT step: language and no_speech_prob
+                r.feed = self._sot_result(r, int(nxt[j]), float(lps[j]), float(plps[j]))
                 continue
             t = int(r.target[r.step]) if r.target is not None else int(nxt[j])
             r.tokens.append(t)
@@ -700,10 +868,23 @@ class STTEngine:
         """Window ``r.win`` of ``r`` is decoded: start the next window (None)
         or complete the request (its windows' texts joined)."""
         toks = [x for x in r.tokens if x != self.eot]
-        r.win_texts.append(self.tok.decode(toks).strip())
-        r.prev_tokens = (r.prev_tokens + toks)[-max(PREV_TOKENS, 1):]
         self.kv.pool.free_seq(r.seq_id)
-        if r.logprobs:
+        # Whisper's no-speech rule, on a freely decoded window (a teacher-forced
+        # one has no log-probabilities): its text is empty, its tokens stay out
+        # of the next window's prompt and of the utterance's avg_logprob
+        gated = False
+        if self.no_speech and r.target is None and r.logprobs and len(r.no_speech_probs) > r.win:
+            mean_lp = float(np.sum(np.asarray(r.logprobs, np.float64))) / len(r.logprobs)
+            gated = r.no_speech_probs[r.win] > self.no_speech_threshold and \
+                mean_lp < self.logprob_threshold
+        if gated:
+            r.gated_windows += 1
+            self.stats["no_speech_windows"] += 1
+            r.win_texts.append("")
+        else:
+            r.win_texts.append(self.tok.decode(toks).strip())
+            r.prev_tokens = (r.prev_tokens + toks)[-max(PREV_TOKENS, 1):]
+        if r.logprobs and not gated:
             # fp64 sum of the window's f32 values; -inf (nothing allowed) stays -inf
             r.lp_sum += float(np.sum(np.asarray(r.logprobs, np.float64)))
             r.lp_n += len(r.logprobs)
@@ -713,6 +894,10 @@ class STTEngine:
             return None
         r.t_done = time.perf_counter()
         r.text = " ".join(t for t in r.win_texts if t)
+        if r.no_speech_probs:
+            r.no_speech_prob = min(r.no_speech_probs)
+        if r.gated_windows and r.gated_windows == r.windows:
+            self.stats["no_speech_utterances"] += 1
         if r.lp_n:
             r.avg_logprob = r.lp_sum / r.lp_n
             if np.isfinite(r.lp_sum):       # a step with nothing allowed is -inf

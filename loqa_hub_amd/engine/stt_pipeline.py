@@ -35,7 +35,8 @@ class _Step:
 
     def __init__(self, rows, B, out, event, entries):
         # out: a graph step's result ring row; a synchronous step's result
-        # (tokens, with the engine's token_logprobs (tokens, log-probabilities))
+        # (tokens, with the engine's token_logprobs (tokens, log-probabilities),
+        # a probing engine (tokens, log-probabilities, probed log-probabilities))
         self.rows, self.B, self.out, self.event, self.entries = rows, B, out, event, entries
 
 
@@ -65,13 +66,17 @@ class STTPipeline:
     def _feed(self, r):
         """(tokens with DEV placeholders, speculative) of r's next step, or None.
         The first ``r.prompt_steps`` steps feed the prompt (the SOT tokens, after
-        a long-form window's previous-text prompt) at most len(SOT) tokens at a
-        time - the captured graphs' per-sequence query limit."""
-        c = self.eng.n_prompt_tokens_per_step
+        a long-form window's previous-text prompt) in ``r.chunks``: at most
+        len(SOT) tokens at a time - the captured graphs' per-sequence query
+        limit. A probing engine's SOT step is never speculated past: the chunk
+        after it exists once that step has retired (``STTEngine._sot_result``),
+        until then the request offers no feed."""
         ps = r.prompt_steps
         k = r.pl_launched
         if k < ps:
-            return list(r.feed[k * c:(k + 1) * c]), False
+            if k >= len(r.chunks):
+                return None
+            return list(r.chunks[k]), False
         k = k - ps + 1                            # 1 = the first step feeding a decoded token
         if r.target is not None:
             if k >= len(r.target):
@@ -136,11 +141,12 @@ class STTPipeline:
         T_pad = ops.mpad_for(T)
         ctx = max(eng.kv.pool.seq_len(r.seq_id) + len(f) for r, f in zip(rows, feeds))
         C = min(eng.cfg.n_text_ctx, -(-ctx // eng.SPLIT_KEYS) * eng.SPLIT_KEYS)
+        sot = [r.pl_launched == r.sot_step for r in rows] if eng.sot_probe else None
         if (B_pad, T_pad, C) not in eng._graphs and eng._graphs_frozen:
-            return self._launch_sync(rows, feeds)
+            return self._launch_sync(rows, feeds, sot)
         g = eng._graph(B_pad, T_pad, C)
         hb = eng.io.stage(g)
-        eng._host_meta(rows, B_pad, T_pad, out=hb, feeds=feeds)
+        eng._host_meta(rows, B_pad, T_pad, out=hb, feeds=feeds, sot=sot)
         stage_feeds(hb, feeds, [r.slot for r in rows], eng.io.trash)
         t_r = time.perf_counter()
         rslot = eng.io.replay(g)
@@ -159,7 +165,7 @@ class STTPipeline:
         eng.stats["decode_steps"] += 1
         return True
 
-    def _launch_sync(self, rows, feeds) -> bool:
+    def _launch_sync(self, rows, feeds, sot=None) -> bool:
         """Bucket without a captured graph (serving never captures): finish
         what is in flight, then one synchronous step through ``STTEngine._step``."""
         if any(DEV in f for f in feeds):
@@ -167,7 +173,7 @@ class STTPipeline:
         saved = [r.feed for r in rows]
         for r, f in zip(rows, feeds):
             r.feed = f
-        res = self.eng._step(rows)
+        res = self.eng._step(rows, sot) if sot is not None else self.eng._step(rows)
         out = res[0] if self.eng.token_logprobs else res
         for r, f in zip(rows, saved):
             r.feed = f
@@ -192,7 +198,11 @@ class STTPipeline:
         if st.event is not None:
             st.event.synchronize()
         res = eng.io.result(st.out, st.B) if st.event is not None else st.out
-        nxt, lps = res if eng.token_logprobs else (res, None)
+        plps = None
+        if eng.sot_probe:
+            nxt, lps, plps = res
+        else:
+            nxt, lps = res if eng.token_logprobs else (res, None)
         eng.stats["gpu_wait_s"] += time.perf_counter() - t0
         done = []
         for b, (r, (k, sp)) in enumerate(zip(st.rows, st.entries)):
@@ -200,6 +210,9 @@ class STTPipeline:
             if r.t_done != 0.0 or r.pl_end:
                 if sp:
                     self.stats["pl_discard"] += 1
+                continue
+            if k == r.sot_step:                  # language and no_speech_prob; the next chunk
+                eng._sot_result(r, int(nxt[b]), float(lps[b]), float(plps[b]))
                 continue
             k -= r.prompt_steps - 1              # token index; < 0: a prompt chunk (logits unused)
             if k < 0:

@@ -176,6 +176,44 @@ class SyntheticTokenizer:
         return self.strings[t] if self.n_special <= t < self.n_real else ""
 
 
+# Whisper-only extension of the synthetic tokenizer, in reserved-filler order:
+# the no-speech token and three more languages beside <|en|>
+WHISPER_PROBE_TOKENS = ["<|nospeech|>", "<|es|>", "<|fr|>", "<|de|>"]
+_LANG_RE = re.compile(r"<\|([a-z]{2,3})\|>")
+
+
+class SyntheticWhisperTokenizer:
+    """A ``SyntheticTokenizer`` whose first reserved filler ids stand for
+    ``WHISPER_PROBE_TOKENS``: what an ``STTEngine`` that reads the
+    start-of-transcript logits needs (a no-speech token, several language
+    tokens). A view of the base tokenizer: its ids, ``n_real``, texts and
+    ``encode`` / ``decode`` are the base's (the claimed ids stay filler there:
+    never encoded, no text), so the LLM side and every grammar mask are
+    untouched."""
+
+    def __init__(self, base: SyntheticTokenizer):
+        if base.vocab_size - base.n_real < len(WHISPER_PROBE_TOKENS):
+            raise ValueError("vocabulary too small for the Whisper probe tokens")
+        self._base = base
+        self._extra = {s: base.n_real + i for i, s in enumerate(WHISPER_PROBE_TOKENS)}
+
+    def __getattr__(self, name):
+        return getattr(self._base, name)
+
+    def token_id(self, s: str) -> int:
+        i = self._extra.get(s)
+        return self._base.token_id(s) if i is None else i
+
+    def language_tokens(self) -> dict:
+        """{language code: token id}, in id order."""
+        out = {"en": self._base.token_id("<|en|>")}
+        for s, i in self._extra.items():
+            m = _LANG_RE.fullmatch(s)
+            if m:
+                out[m.group(1)] = i
+        return out
+
+
 # ---------------------------------------------------------------------------
 # Real checkpoints: the Hugging Face ``tokenizer.json`` shipped with them
 TOKENIZER_FILE = "tokenizer.json"
@@ -322,6 +360,31 @@ class HFTokenizer:
 
     def token_text(self, t: int) -> str:
         return self._text[t] if 0 <= t < self.n_real else ""
+
+    def language_tokens(self) -> dict:
+        """{language code: token id} of a multilingual Whisper tokenizer, in id
+        order: the generation config's ``lang_to_id`` when it has one, else the
+        added tokens between ``<|startoftranscript|>`` and ``<|translate|>``
+        that look like ``<|xx|>``."""
+        l2i = self.generation_config.get("lang_to_id")
+        if isinstance(l2i, dict) and l2i:
+            found = {}
+            for k, i in l2i.items():
+                m = _LANG_RE.fullmatch(k)
+                if m and 0 <= int(i) < self.vocab_size:
+                    found[m.group(1)] = int(i)
+            return dict(sorted(found.items(), key=lambda kv: kv[1]))
+        sot = self._t.token_to_id("<|startoftranscript|>")
+        end = self._t.token_to_id("<|translate|>")
+        if sot is None or end is None:
+            return {}
+        out = {}
+        for i in sorted(self._added):
+            t = self._added[i]
+            m = _LANG_RE.fullmatch(str(getattr(t, "content", t)))
+            if sot < i < end and m:
+                out[m.group(1)] = i
+        return out
 
     def sampling_mask(self, keep: tuple = ()):
         """bool [vocab_size]: the tokens free (unconstrained) sampling may

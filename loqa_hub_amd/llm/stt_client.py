@@ -52,7 +52,9 @@ class STTClient:
     def __init__(self, base_url: str = "", language: str = "en", *,
                  client: HTTPClient | None = None, timeout: float = 30.0):
         self.base_url = (base_url or "http://localhost:8000").rstrip("/")
-        self.language = language or "en"
+        # "auto": an empty language field, the reference's pass-through (a
+        # Whisper service then detects the language)
+        self.language = "" if (language or "").strip().lower() == "auto" else language or "en"
         self.client = client or AiohttpClient()
         self.timeout = timeout
 

@@ -29,6 +29,11 @@ class TranscriptionResult:
     wake_word_variant: str = ""
     needs_confirmation: bool = False
     avg_logprob: float | None = None   # mean Whisper token log-probability (acoustic confidence)
+    # read from the Whisper start-of-transcript logits (gpu backend with
+    # language detection or the no-speech rule; else None)
+    language: str | None = None
+    language_prob: float | None = None
+    no_speech_prob: float | None = None
 
 
 @dataclass
@@ -92,17 +97,22 @@ def post_process_transcription(raw: str) -> PostProcessingResult:
 
 
 def to_transcription_result(raw: str, avg_logprob: float | None = None,
-                            confirm_below: float = CONFIRMATION_THRESHOLD) -> TranscriptionResult:
+                            confirm_below: float = CONFIRMATION_THRESHOLD, *,
+                            language: str | None = None, language_prob: float | None = None,
+                            no_speech_prob: float | None = None) -> TranscriptionResult:
     """``avg_logprob`` (the on-device Whisper decode's mean token
     log-probability): the confidence is the geometric-mean token probability
     ``min(1, exp(avg_logprob))`` instead of the text heuristic, and a
     confirmation is needed below ``confirm_below``. None: the reference's
-    heuristic and threshold. The wake-word-only rule holds either way."""
+    heuristic and threshold. The wake-word-only rule holds either way.
+    ``language`` / ``language_prob`` / ``no_speech_prob``: what the decoder read
+    at the start-of-transcript position, carried as they are."""
     p = post_process_transcription(raw)
+    probe = dict(language=language, language_prob=language_prob, no_speech_prob=no_speech_prob)
     if avg_logprob is None:
         return TranscriptionResult(p.cleaned_text, p.confidence_estimate, p.wake_word_detected,
-                                   p.wake_word_variant, p.needs_confirmation)
+                                   p.wake_word_variant, p.needs_confirmation, **probe)
     conf = min(1.0, math.exp(avg_logprob))
     confirm = conf < confirm_below or (p.wake_word_detected and p.cleaned_text == "")
     return TranscriptionResult(p.cleaned_text, conf, p.wake_word_detected, p.wake_word_variant,
-                               confirm, avg_logprob)
+                               confirm, avg_logprob, **probe)

@@ -338,6 +338,53 @@ def masked_argmax_logprob(logits: torch.Tensor, mask: torch.Tensor | None = None
     return out, lp
 
 
+def masked_argmax_logprob_probe(logits: torch.Tensor, mask: torch.Tensor | None,
+                                mask_rows: torch.Tensor | None, probe: torch.Tensor,
+                                token_ids: torch.Tensor | None = None
+                                ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``masked_argmax_logprob`` (the same two results, bit for bit) plus, per
+    row, the log-softmax of one fixed column BEFORE the mask:
+    ``x[b, probe[b]] - logsumexp(x[b, :])`` over all columns, in fp32 (Whisper's
+    log ``no_speech_prob`` at the start-of-transcript row). ``probe``: int32 [B];
+    a row with ``probe[b] < 0`` gives exactly +0.0 and does not pay for the
+    second sum, a row of -inf only gives -inf. A column >= V is a ValueError
+    when ``probe`` is a host tensor; on the device such a row counts as < 0.
+    Returns (int32 [B], float32 [B], float32 [B])."""
+    if token_ids is not None:
+        assert token_ids.dtype == torch.int32 and token_ids.is_contiguous()
+        assert token_ids.numel() >= logits.shape[-1] and token_ids.device == logits.device
+    assert logits.dim() == 2 and logits.stride(-1) == 1
+    B, V = logits.shape
+    assert probe.dtype == torch.int32 and probe.is_contiguous() and probe.numel() == B
+    assert probe.device == logits.device
+    if probe.device.type == "cpu" and B and int(probe.max()) >= V:
+        raise ValueError(f"probe column {int(probe.max())} is outside the {V} logits")
+    if not _gpu(logits):
+        return ref.masked_argmax_logprob_probe(logits, mask, mask_rows, probe, token_ids)
+    W = 0
+    if mask is not None:
+        assert mask.dtype == torch.int32 and mask.is_contiguous()
+        W = mask.shape[-1]
+        assert W * 32 >= V
+        if mask_rows is not None:
+            assert mask_rows.dtype == torch.int32 and mask_rows.numel() == B
+        else:
+            assert mask.shape[0] >= B
+    is_bf16 = logits.dtype == torch.bfloat16
+    assert is_bf16 or logits.dtype == torch.float32
+    out = torch.empty(B, dtype=torch.int32, device=logits.device)
+    lp = torch.empty(B, dtype=torch.float32, device=logits.device)
+    plp = torch.empty(B, dtype=torch.float32, device=logits.device)
+    chunks = (V + ARG_CHUNK - 1) // ARG_CHUNK
+    # 32-byte chunk records [B, chunks] (written before they are read)
+    ws = torch.empty(B * chunks * 4, dtype=torch.int64, device=logits.device) if chunks > 1 else None
+    check(kernels().loqa_masked_argmax_lse_probe(
+        ptr(logits), int(is_bf16), logits.stride(0), B, V, ptr(mask), ptr(mask_rows), W,
+        ptr(probe), ptr(out), ptr(lp), ptr(plp), ptr(ws), ptr(token_ids), stream_ptr(logits)),
+        "masked_argmax_lse_probe")
+    return out, lp, plp
+
+
 # -------------------------------------------------------------------- audio
 def pcm16_to_f32_sumsq(pcm: torch.Tensor, offsets: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     """pcm: int16 [N] (concatenated segments), offsets: int64 [S+1].

@@ -160,6 +160,14 @@ _KERNEL_SIGS = {
     # (out, logprobs, n, res, stride, res_lp, lp_stride, nres, ctr, row_slot, last_tok, stream)
     "loqa_step_publish_lp": [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
                              c_void_p, c_void_p, c_void_p, c_void_p],
+    "loqa_masked_argmax_lse_probe": [c_void_p, c_int, c_ll, c_int, c_int, c_void_p, c_void_p, c_int,
+                                     # (..., probe, out_idx, out_logprob, out_probe, workspace,
+                                     #  token_ids, stream)
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p],
+    # (out, lp, lp2, n, res, stride, res_lp, lp_stride, plane, nres, ctr, row_slot, last_tok, stream)
+    "loqa_step_publish_lp2": [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                              c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
 }
 
 # (argtypes, restype) of the custom all-reduce entry points (in the kernels library)

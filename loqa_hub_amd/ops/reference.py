@@ -180,6 +180,22 @@ def masked_argmax_logprob(logits, mask=None, mask_rows=None, token_ids=None):
     return idx, lp
 
 
+def masked_argmax_logprob_probe(logits, mask, mask_rows, probe, token_ids=None):
+    """``masked_argmax_logprob`` plus ``x[b, probe[b]] - logsumexp(x[b, :])`` over
+    ALL columns (the mask ignored), in fp32. ``probe[b] < 0`` (or >= V): +0.0;
+    a probed logit of -inf or a row of -inf only: -inf (never NaN)."""
+    idx, lp = masked_argmax_logprob(logits, mask, mask_rows, token_ids)
+    x = logits.float()
+    B, V = x.shape
+    p = probe.long()
+    on = (p >= 0) & (p < V)
+    px = x.gather(1, p.clamp(0, V - 1)[:, None])[:, 0]
+    plp = px - torch.logsumexp(x, dim=-1)
+    plp = torch.where(torch.isinf(px) & (px < 0), torch.full_like(plp, float("-inf")), plp)
+    plp = torch.where(on, plp, torch.zeros_like(plp))
+    return idx, lp, plp
+
+
 def unpack_mask(m: torch.Tensor, V: int) -> torch.Tensor:
     """int32 words [..., W] -> bool [..., V]"""
     shifts = torch.arange(32, device=m.device, dtype=torch.int32)

@@ -113,7 +113,10 @@ def build_gpu_processor(cfg: Config, nats, device: str = "cuda:0", tts=None, *, 
             if (g.llm_checkpoint and llm is None) else None
     stt = STTEngine(scfg, device, seed=g.seed, max_batch=g.max_batch, use_graphs=g.use_graphs,
                     weights=sw, tokenizer=g.tokenizer("stt", scfg.vocab_size),
-                    language=cfg.stt.language, token_logprobs=g.stt_confidence == "acoustic")
+                    language=cfg.stt.language, token_logprobs=g.stt_confidence == "acoustic",
+                    languages=g.stt_languages or None, no_speech=g.stt_no_speech == "on",
+                    no_speech_threshold=g.stt_no_speech_threshold,
+                    logprob_threshold=g.stt_logprob_threshold)
     if llm is None:
         llm = LLMEngine(lcfg, device, seed=g.seed, max_seqs=g.max_batch, weights=lw,
                         max_seq_len=g.max_seq_len, block_size=g.kv_block, use_graphs=g.use_graphs,
@@ -123,7 +126,8 @@ def build_gpu_processor(cfg: Config, nats, device: str = "cuda:0", tts=None, *, 
                          f"{getattr(llm, 'weight_dtype', 'bf16')} weights")
     if tts == "auto":
         tts = build_tts(cfg, device)
-    pipe = VoicePipeline(stt, llm, nats, stt_confirm_below=g.stt_confirm_below)
+    pipe = VoicePipeline(stt, llm, nats, stt_confirm_below=g.stt_confirm_below,
+                         stt_acoustic=g.stt_confidence == "acoustic")
     pipe.warmup()
     if tts is not None and hasattr(tts, "warmup_graphs"):
         tts.warmup_graphs()         # VITS graph buckets of typical replies

@@ -89,6 +89,7 @@ class GPUVoiceProcessor:
         pipeline.batch_window, pipeline.max_batch = batch_window, max_batch
         self.stats = {"utterances": 0, "errors": 0, "bridge_sessions": 0, "bridge_ack": 0,
                       "bridge_fallback": 0, "interrupted": 0, "stt_low_confidence": 0,
+                      "stt_no_speech": 0,
                       "progressive": 0, "first_audio_ms_sum": 0.0, "first_audio_n": 0}
         # a list that collects every finished PipelineJob (phase timestamps for
         # a benchmark's per-phase breakdown); None: not collected
@@ -194,6 +195,11 @@ class GPUVoiceProcessor:
             # None with the heuristic, HUB_STT_CONFIDENCE)
             r.metrics["stt"] = {"confidence": tr.confidence_estimate,
                                 "avg_logprob": tr.avg_logprob}
+            if tr.no_speech_prob is not None:    # the engine reads the SOT logits
+                r.metrics["stt"].update(language=tr.language, language_prob=tr.language_prob,
+                                        no_speech_prob=tr.no_speech_prob)
+            if j.no_speech:                      # dropped by the no-speech rule: no LLM pass
+                self.stats["stt_no_speech"] += 1
             below = CONFIRMATION_THRESHOLD      # the heuristic keeps the reference's threshold
             if tr.avg_logprob is not None:
                 below = getattr(self.pipeline, "stt_confirm_below", below)

@@ -122,7 +122,12 @@ def config_2_or_5(cfg_id: int, args, dev, nats, tp_info=None) -> dict:
     if getattr(args, "streams", 0):
         streams = args.streams
     t0 = time.perf_counter()
-    stt = STTEngine(whisper_config(stt_name), dev, seed=0, max_batch=8)
+    # --stt-probe: the decoder reads the start-of-transcript logits ("on": fixed
+    # language, no_speech_prob recorded; "auto": language detection as well)
+    probe = getattr(args, "stt_probe", "off")
+    stt = STTEngine(whisper_config(stt_name), dev, seed=0, max_batch=8,
+                    **({} if probe == "off" else
+                       {"sot_probe": True, "language": "auto" if probe == "auto" else "en"}))
     tp = tp_info.world if tp_info is not None else 1
     if tp > 1:
         from loqa_hub_amd.parallel.tp_serving import build_tp_llm
@@ -166,6 +171,11 @@ def config_2_or_5(cfg_id: int, args, dev, nats, tp_info=None) -> dict:
         "latency_ms_p50": round(float(np.median(lat)), 1),
         "latency_ms_p90": round(float(np.percentile(lat, 90)), 1),
         "stt_ms_mean": round(float(np.mean(stt_ms)), 1),
+        "stt_probe": probe,
+        # the Whisper decode alone: decoder start to transcript
+        "stt_decode_ms_mean": round(float(np.mean([(j.t["stt_done"] - j.t["dec0"]) * 1e3
+                                                   for j in jobs if "dec0" in j.t])), 2),
+        "stt_decode_steps": stt.stats["decode_steps"],
         "ms_per_added_command_e2e_marginal": None if st["e2e_marginal_ms_per_added_command"] is None
         else round(st["e2e_marginal_ms_per_added_command"], 2),
         "ms_per_added_command_ref_equiv": st["ref_equiv_ms_per_added_command"],
@@ -361,6 +371,8 @@ def main() -> int:
                     help="TP ranks share cuda:0 (spawned here when not under torchrun)")
     ap.add_argument("--compact", action="store_true",
                     help="TP: single-copy fused weights (needed when ranks share a GPU)")
+    ap.add_argument("--stt-probe", choices=["off", "on", "auto"], default="off",
+                    help="configs 2 / 5: STTEngine(sot_probe=True) (auto: with language detection)")
     ap.add_argument("--weights", choices=["bf16", "fp8", "mxfp4"], default="bf16",
                     help="configs 2 / 5, --tp 1: LLM projection weights (fp8: e4m3 weight streams; "
                          "mxfp4: 4-bit projections, fp8 lm_head; secondary figures, never the headline)")
