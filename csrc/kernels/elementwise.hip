@@ -10,6 +10,7 @@
 // All bf16 traffic is 8-16 bytes per lane (guide G13).
 #include "common.h"
 #include <float.h>
+#include <type_traits>
 
 // ---------------------------------------------------------------- K14 SwiGLU
 // in: [T, 2F] = [gate | up], out: [T, F]. 2-D grid (x: 8-wide column vectors,
@@ -323,20 +324,44 @@ extern "C" int loqa_pcm16_f32_pad(const void* pcm, float* out, const long long* 
 }
 
 // --------------------------------------------------- K15 grammar-masked argmax
+// One row scan in three modes behind loqa_masked_argmax (MODE 0), _lse (1) and
+// _lse_probe (2). The modes share the arithmetic and its order, so a higher
+// mode returns the lower modes' results bit for bit.
 // logits: [B, V] (bf16 if is_bf16 else f32), row stride ld elements.
 // mask: [*, W] uint32 bitmask (bit v%32 of word v/32 = token v allowed), or null;
 // mask_rows: optional per-row index into the mask table (rows share the
-// precomputed grammar-state masks). Each row is split over ARG_CHUNK-token
-// workgroups (a 128k vocabulary -> 16 workgroups per row, so B=16 rows fill the
-// GPU); each workgroup folds its best (value, index) into one 64-bit atomicMax
-// of (order-preserving float key << 32 | ~index) - ties resolve to the lowest
-// index like torch.argmax. out_idx[b] = argmax over allowed tokens (or -1).
+// precomputed grammar-state masks).
+// Every mode: out_idx[b] = argmax over the allowed tokens, or -1 when nothing is
+// allowed. A candidate is (order-preserving float key << 32 | ~index) folded
+// with max: ties resolve to the lowest index like torch.argmax.
 // token_ids (optional, int32 [V]): the columns are a gathered subset of the
 // vocabulary (the compact sampling head) and out_idx[b] = token_ids[column];
 // the record keeps the column, so with ascending ids a tie still goes to the
-// lowest token id. A row that fits one chunk (V <= ARG_CHUNK) is one
-// workgroup, which writes out_idx[b] itself: no atomic, no zeroed workspace,
-// no unpack launch.
+// lowest token id.
+// MODE >= 1: out_logprob[b] = x[winner] - logsumexp(x over the ALLOWED columns),
+// the log-softmax of the selected token after the mask. The winner is the
+// maximum, so with m = max and s = sum exp(x - m) the result is -log(s): +0.0f
+// when the winner is the only allowed token (s == 1); -inf, never NaN, when
+// nothing is allowed or the winner is -inf. Every logit is read once and costs
+// one expf (online softmax per thread); all arithmetic is f32.
+// MODE 2: out_probe[b] = x[b, probe[b]] - logsumexp(x[b, 0..V-1] over ALL
+// columns, the mask ignored): the log-softmax of one fixed column before the
+// mask (Whisper's log no_speech_prob at the start-of-transcript row). A probing
+// row keeps a second pair (am, as) over all columns in the same pass; the mask
+// bits only decide whether a term joins the first pair too. The thread that
+// meets column probe[b] keeps that logit in px, all others hold -inf, so a max
+// over threads and chunk records carries it to the end unchanged. The result is
+// (px - am) - logf(as): -inf for a probed logit or a whole row of -inf. A row
+// with probe[b] < 0 or >= V writes +0.0f and skips the second sum; the test is
+// per row (blockIdx.y), so wave-uniform.
+// A row is split over ARG_CHUNK-token workgroups (a 128k vocabulary -> 16 per
+// row, so B=16 rows fill the GPU). Each reduces its tokens to one record (8, 16
+// or 32 bytes by mode) in a fixed order: vector groups in column order, the
+// shuffle tree 32 -> 1, the waves in wave order. A row of one chunk finishes
+// there (SINGLE): one launch, no workspace. A wider row in MODE 0 folds its
+// records with atomicMax into a zeroed word per row, which a small launch
+// unpacks; in MODE >= 1 it writes them to workspace[b][chunk] and a finalize
+// launch merges them in chunk order: no memset, no atomics, bitwise repeatable.
 #define ARG_CHUNK 8192
 #define ARG_THREADS 256
 
@@ -351,130 +376,6 @@ __device__ __forceinline__ int argunpack(unsigned long long p, const int* __rest
   const int col = (int)(0xFFFFFFFFu - (uint32_t)(p & 0xFFFFFFFFull));
   return token_ids ? token_ids[col] : col;
 }
-
-// SINGLE: gridDim.x == 1 (V <= ARG_CHUNK); the workgroup writes out_idx[b]
-template <bool BF16, bool SINGLE>
-__global__ __launch_bounds__(ARG_THREADS) void masked_argmax_kernel(
-    const void* __restrict__ logits, long long ld, int V, const uint32_t* __restrict__ mask,
-    const int* __restrict__ mask_rows, int W, unsigned long long* __restrict__ packed,
-    const int* __restrict__ token_ids, int* __restrict__ out_idx) {
-  __shared__ unsigned long long sbest[ARG_THREADS / 64];
-  const int b = blockIdx.y;
-  const int v_begin = blockIdx.x * ARG_CHUNK;
-  const int v_end = min(V, v_begin + ARG_CHUNK);
-  const uint32_t* m = nullptr;
-  if (mask) m = mask + (size_t)(mask_rows ? mask_rows[b] : b) * W;
-  unsigned long long best = 0;
-  if (BF16) {
-    const bf16_t* row = reinterpret_cast<const bf16_t*>(logits) + (size_t)b * ld;
-    for (int v0 = v_begin + threadIdx.x * 8; v0 < v_end; v0 += ARG_THREADS * 8) {
-      if (v0 + 8 <= v_end && (ld % 8 == 0)) {
-        float f[8];
-        unpack8(*reinterpret_cast<const uint4*>(row + v0), f);
-        const uint32_t bits = m ? (m[v0 >> 5] >> (v0 & 31)) & 0xffu : 0xffu;
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          if ((bits >> j) & 1u) best = max(best, argpack(f[j], v0 + j));
-      } else {
-        for (int v = v0; v < min(v_end, v0 + 8); ++v)
-          if (!m || ((m[v >> 5] >> (v & 31)) & 1u)) best = max(best, argpack(bf2f(row[v]), v));
-      }
-    }
-  } else {
-    const float* row = reinterpret_cast<const float*>(logits) + (size_t)b * ld;
-    for (int v0 = v_begin + threadIdx.x * 4; v0 < v_end; v0 += ARG_THREADS * 4) {
-      if (v0 + 4 <= v_end && (ld % 4 == 0)) {
-        const float4 f = *reinterpret_cast<const float4*>(row + v0);
-        const uint32_t bits = m ? (m[v0 >> 5] >> (v0 & 31)) & 0xfu : 0xfu;
-        if (bits & 1u) best = max(best, argpack(f.x, v0));
-        if (bits & 2u) best = max(best, argpack(f.y, v0 + 1));
-        if (bits & 4u) best = max(best, argpack(f.z, v0 + 2));
-        if (bits & 8u) best = max(best, argpack(f.w, v0 + 3));
-      } else {
-        for (int v = v0; v < min(v_end, v0 + 4); ++v)
-          if (!m || ((m[v >> 5] >> (v & 31)) & 1u)) best = max(best, argpack(row[v], v));
-      }
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long other = __shfl_xor(best, o, 64);
-    best = max(best, other);
-  }
-  if ((threadIdx.x & 63) == 0) sbest[threadIdx.x >> 6] = best;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int i = 1; i < ARG_THREADS / 64; ++i) best = max(best, sbest[i]);
-    if (SINGLE)
-      out_idx[b] = argunpack(best, token_ids);
-    else if (best)
-      atomicMax(packed + b, best);
-  }
-}
-
-__global__ void argmax_unpack_kernel(const unsigned long long* __restrict__ packed, int B,
-                                     const int* __restrict__ token_ids, int* __restrict__ out_idx) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b < B) out_idx[b] = argunpack(packed[b], token_ids);
-}
-
-template <bool SINGLE>
-static void launch_masked_argmax(int is_bf16, dim3 grid, hipStream_t s, const void* logits,
-                                 long long ld, int V, const uint32_t* mask, const int* mask_rows,
-                                 int W, unsigned long long* packed, const int* token_ids,
-                                 int* out_idx) {
-  if (is_bf16)
-    hipLaunchKernelGGL((masked_argmax_kernel<true, SINGLE>), grid, dim3(ARG_THREADS), 0, s, logits,
-                       ld, V, mask, mask_rows, W, packed, token_ids, out_idx);
-  else
-    hipLaunchKernelGGL((masked_argmax_kernel<false, SINGLE>), grid, dim3(ARG_THREADS), 0, s, logits,
-                       ld, V, mask, mask_rows, W, packed, token_ids, out_idx);
-}
-
-// workspace: >= B * 8 bytes (device); only read when V > ARG_CHUNK.
-// token_ids: null, or int32 [V] (see above)
-extern "C" int loqa_masked_argmax(const void* logits, int is_bf16, long long ld, int B, int V,
-                                  const uint32_t* mask, const int* mask_rows, int W, int* out_idx,
-                                  void* workspace, const int* token_ids, hipStream_t s) {
-  if (B <= 0) return 0;
-  if (V <= 0 || (mask && W * 32 < V) || !out_idx) return (int)hipErrorInvalidValue;
-  if (V <= ARG_CHUNK) {
-    launch_masked_argmax<true>(is_bf16, dim3(1, B), s, logits, ld, V, mask, mask_rows, W, nullptr,
-                               token_ids, out_idx);
-    return (int)hipGetLastError();
-  }
-  if (!workspace) return (int)hipErrorInvalidValue;
-  unsigned long long* packed = (unsigned long long*)workspace;
-  hipError_t e = hipMemsetAsync(packed, 0, sizeof(unsigned long long) * B, s);
-  if (e != hipSuccess) return (int)e;
-  launch_masked_argmax<false>(is_bf16, dim3((V + ARG_CHUNK - 1) / ARG_CHUNK, B), s, logits, ld, V,
-                              mask, mask_rows, W, packed, token_ids, out_idx);
-  e = hipGetLastError();
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(argmax_unpack_kernel, dim3((B + 63) / 64), dim3(64), 0, s, packed, B, token_ids,
-                     out_idx);
-  return (int)hipGetLastError();
-}
-
-// ------------------------------------- masked argmax + selected log-probability
-// loqa_masked_argmax_lse: out_idx[b] as loqa_masked_argmax (same packed record,
-// same tie rule, token_ids, -1) and out_logprob[b] = x[winner] - logsumexp(x
-// over the ALLOWED tokens of columns 0..V-1), the log-softmax of the selected
-// token after the mask. The winner is the maximum, so with m = max and
-// s = sum exp(x - m) over allowed tokens the result is -log(s); a row whose only
-// allowed token is the winner has s == 1 and gives +0.0f. Nothing allowed, or a
-// winner of -inf, gives -inf (never NaN).
-// Every logit is read once and costs one expf (online softmax per thread, plus
-// one rescaling expf when a vector group raises the thread's maximum); all
-// arithmetic is f32. A workgroup reduces its ARG_CHUNK tokens to one record
-// (packed best, chunk max, chunk sum) in a fixed order; a row of one chunk
-// finishes there, a wider row writes the record to workspace[b][chunk] and a
-// finalize launch merges the row's records in chunk order: no memset, no
-// atomics, and results that are bitwise repeatable.
-struct ArgLse {
-  unsigned long long best;
-  float m, s;
-};
 
 __device__ __forceinline__ void lse_add(float& m, float& s, float x) {
   if (x == -INFINITY) return;     // weight 0 (and keeps inf - inf out of the sum)
@@ -507,10 +408,27 @@ __device__ __forceinline__ void lse_add_group(float& m, float& s, const float (&
     if ((bits >> j) & 1u) s += expf(f[j] - m);   // m finite: -inf gives 0
 }
 
+// s = s * exp(m - mm) + s2 * exp(m2 - mm) with its roundings spelled out. Left
+// to -ffp-contract=fast the compiler decides per call site which of the two
+// products an fma absorbs, or, where it packs the two multiplies into one
+// instruction, that none is, and the bits of the sum follow that choice.
+// FMA: the first product rounds, the second is fused (the masked pair inside a
+// workgroup); otherwise both products round (the all-column pair, and the
+// merge of chunk records). These are the forms the three hand-copied kernels
+// had been compiled to; the results are held to those bits.
+template <bool FMA>
 __device__ __forceinline__ void lse_merge(float& m, float& s, float m2, float s2) {
   const float mm = fmaxf(m, m2);
-  if (mm == -INFINITY) return;    // both empty: s == s2 == 0
-  s = s * expf(m - mm) + s2 * expf(m2 - mm);
+  float r;
+  if constexpr (FMA) {
+    r = fmaf(s2, expf(m2 - mm), s * expf(m - mm));
+  } else {
+#pragma clang fp contract(off)
+    r = s * expf(m - mm) + s2 * expf(m2 - mm);
+  }
+  // both empty: s == s2 == 0 stays (r is NaN there). A select, not an early
+  // return: a merge in the shuffle tree must not become a branch.
+  s = mm == -INFINITY ? s : r;
   m = mm;
 }
 
@@ -518,360 +436,228 @@ __device__ __forceinline__ float lse_logprob(unsigned long long best, float m, f
   return (best && m != -INFINITY) ? 0.f - logf(s) : -INFINITY;
 }
 
-template <bool BF16, bool SINGLE>
-__global__ __launch_bounds__(ARG_THREADS) void masked_argmax_lse_kernel(
-    const void* __restrict__ logits, long long ld, int V, const uint32_t* __restrict__ mask,
-    const int* __restrict__ mask_rows, int W, ArgLse* __restrict__ part,
-    const int* __restrict__ token_ids, int* __restrict__ out_idx, float* __restrict__ out_logprob) {
-  __shared__ ArgLse sred[ARG_THREADS / 64];
-  const int b = blockIdx.y;
-  const int v_begin = blockIdx.x * ARG_CHUNK;
-  const int v_end = min(V, v_begin + ARG_CHUNK);
-  const uint32_t* m = nullptr;
-  if (mask) m = mask + (size_t)(mask_rows ? mask_rows[b] : b) * W;
-  unsigned long long best = 0;
-  float mx = -INFINITY, sum = 0.f;
-  if (BF16) {
-    const bf16_t* row = reinterpret_cast<const bf16_t*>(logits) + (size_t)b * ld;
-    for (int v0 = v_begin + threadIdx.x * 8; v0 < v_end; v0 += ARG_THREADS * 8) {
-      if (v0 + 8 <= v_end && (ld % 8 == 0)) {
-        float f[8];
-        unpack8(*reinterpret_cast<const uint4*>(row + v0), f);
-        const uint32_t bits = m ? (m[v0 >> 5] >> (v0 & 31)) & 0xffu : 0xffu;
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          if ((bits >> j) & 1u) best = max(best, argpack(f[j], v0 + j));
-        lse_add_group<8>(mx, sum, f, bits);
-      } else {
-        for (int v = v0; v < min(v_end, v0 + 8); ++v)
-          if (!m || ((m[v >> 5] >> (v & 31)) & 1u)) {
-            const float x = bf2f(row[v]);
-            best = max(best, argpack(x, v));
-            lse_add(mx, sum, x);
-          }
-      }
-    }
-  } else {
-    const float* row = reinterpret_cast<const float*>(logits) + (size_t)b * ld;
-    for (int v0 = v_begin + threadIdx.x * 4; v0 < v_end; v0 += ARG_THREADS * 4) {
-      if (v0 + 4 <= v_end && (ld % 4 == 0)) {
-        const float4 f4 = *reinterpret_cast<const float4*>(row + v0);
-        const float f[4] = {f4.x, f4.y, f4.z, f4.w};
-        const uint32_t bits = m ? (m[v0 >> 5] >> (v0 & 31)) & 0xfu : 0xfu;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if ((bits >> j) & 1u) best = max(best, argpack(f[j], v0 + j));
-        lse_add_group<4>(mx, sum, f, bits);
-      } else {
-        for (int v = v0; v < min(v_end, v0 + 4); ++v)
-          if (!m || ((m[v >> 5] >> (v & 31)) & 1u)) {
-            const float x = row[v];
-            best = max(best, argpack(x, v));
-            lse_add(mx, sum, x);
-          }
-      }
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long other = __shfl_xor(best, o, 64);
-    best = max(best, other);
-    const float m2 = __shfl_xor(mx, o, 64), s2 = __shfl_xor(sum, o, 64);
-    lse_merge(mx, sum, m2, s2);
-  }
-  if ((threadIdx.x & 63) == 0) sred[threadIdx.x >> 6] = ArgLse{best, mx, sum};
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int i = 1; i < ARG_THREADS / 64; ++i) {
-      best = max(best, sred[i].best);
-      lse_merge(mx, sum, sred[i].m, sred[i].s);
-    }
-    if (SINGLE) {
-      out_idx[b] = argunpack(best, token_ids);
-      out_logprob[b] = lse_logprob(best, mx, sum);
-    } else {
-      part[(size_t)b * gridDim.x + blockIdx.x] = ArgLse{best, mx, sum};
-    }
-  }
-}
-
-// one thread per row: the row's chunk records, merged in chunk order
-__global__ void argmax_lse_finalize_kernel(const ArgLse* __restrict__ part, int B, int chunks,
-                                           const int* __restrict__ token_ids,
-                                           int* __restrict__ out_idx,
-                                           float* __restrict__ out_logprob) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
-  const ArgLse* p = part + (size_t)b * chunks;
-  unsigned long long best = p[0].best;
-  float mx = p[0].m, sum = p[0].s;
-  for (int c = 1; c < chunks; ++c) {
-    best = max(best, p[c].best);
-    lse_merge(mx, sum, p[c].m, p[c].s);
-  }
-  out_idx[b] = argunpack(best, token_ids);
-  out_logprob[b] = lse_logprob(best, mx, sum);
-}
-
-template <bool SINGLE>
-static void launch_masked_argmax_lse(int is_bf16, dim3 grid, hipStream_t s, const void* logits,
-                                     long long ld, int V, const uint32_t* mask,
-                                     const int* mask_rows, int W, ArgLse* part,
-                                     const int* token_ids, int* out_idx, float* out_logprob) {
-  if (is_bf16)
-    hipLaunchKernelGGL((masked_argmax_lse_kernel<true, SINGLE>), grid, dim3(ARG_THREADS), 0, s,
-                       logits, ld, V, mask, mask_rows, W, part, token_ids, out_idx, out_logprob);
-  else
-    hipLaunchKernelGGL((masked_argmax_lse_kernel<false, SINGLE>), grid, dim3(ARG_THREADS), 0, s,
-                       logits, ld, V, mask, mask_rows, W, part, token_ids, out_idx, out_logprob);
-}
-
-// workspace: >= B * ceil(V / ARG_CHUNK) * 16 bytes (device, 8-byte aligned);
-// only touched when V > ARG_CHUNK, and needs no initialisation.
-extern "C" int loqa_masked_argmax_lse(const void* logits, int is_bf16, long long ld, int B, int V,
-                                      const uint32_t* mask, const int* mask_rows, int W,
-                                      int* out_idx, float* out_logprob, void* workspace,
-                                      const int* token_ids, hipStream_t s) {
-  if (B <= 0) return 0;
-  if (V <= 0 || ld < V || (mask && W * 32 < V) || !out_idx || !out_logprob)
-    return (int)hipErrorInvalidValue;
-  if (V <= ARG_CHUNK) {
-    launch_masked_argmax_lse<true>(is_bf16, dim3(1, B), s, logits, ld, V, mask, mask_rows, W,
-                                   nullptr, token_ids, out_idx, out_logprob);
-    return (int)hipGetLastError();
-  }
-  if (!workspace) return (int)hipErrorInvalidValue;
-  const int chunks = (V + ARG_CHUNK - 1) / ARG_CHUNK;
-  launch_masked_argmax_lse<false>(is_bf16, dim3(chunks, B), s, logits, ld, V, mask, mask_rows, W,
-                                  (ArgLse*)workspace, token_ids, out_idx, out_logprob);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(argmax_lse_finalize_kernel, dim3((B + 63) / 64), dim3(64), 0, s,
-                     (const ArgLse*)workspace, B, chunks, token_ids, out_idx, out_logprob);
-  return (int)hipGetLastError();
-}
-
-// ------------------------- masked argmax + log-probability + one probed column
-// loqa_masked_argmax_lse_probe: out_idx[b] and out_logprob[b] exactly as
-// loqa_masked_argmax_lse (the same masked (best, m, s) arithmetic in the same
-// order, the same chunk-record merge order: bit for bit), plus
-// out_probe[b] = x[b, probe[b]] - logsumexp(x[b, 0..V-1] over ALL columns, the
-// mask ignored): the log-softmax of one fixed column before the mask (Whisper's
-// log no_speech_prob at the start-of-transcript row).
-// A probing row keeps a second running (m, s) over all columns in the same
-// pass: each logit is still loaded once, the mask bits only decide whether a
-// term joins the first pair too. The thread whose vector group holds column
-// probe[b] keeps that logit; every other thread holds -inf for it, so a maximum
-// over the row's threads and chunk records moves it to the finalizing thread
-// unchanged. The result is (x[p] - m) - logf(s): -inf for a probed logit of
-// -inf or a row of -inf only (never NaN).
-// A row with probe[b] < 0 or >= V writes +0.0f and skips the second sum; the
-// branch is per row (blockIdx.y), so it is wave-uniform.
-// No memset, no atomics, bitwise repeatable, as the sibling.
-struct ArgLseProbe {
-  unsigned long long best;
-  float m, s;       // allowed columns
-  float am, as;     // all columns (probing rows)
-  float px, pad;    // the probed logit, -inf where this record does not hold it
-};
-
 __device__ __forceinline__ float lse_probe_logprob(bool probing, float px, float am, float as) {
   if (!probing) return 0.f;
   if (am == -INFINITY) return -INFINITY;      // every logit -inf (px too)
   return (px - am) - logf(as);                // px == -inf: -inf; as >= 1
 }
 
-template <bool BF16, bool SINGLE>
-__global__ __launch_bounds__(ARG_THREADS) void masked_argmax_lse_probe_kernel(
+// a chunk's record, as it lies in LDS and in the workspace
+template <int MODE> struct ArgRec;
+template <> struct ArgRec<0> { unsigned long long best; };
+template <> struct ArgRec<1> { unsigned long long best; float m, s; };
+template <> struct ArgRec<2> {
+  unsigned long long best;
+  float m, s;       // allowed columns
+  float am, as;     // all columns (probing rows)
+  float px, pad;    // the probed logit, -inf where this record does not hold it
+};
+
+// The running state of a thread, a wave, a chunk or a row: a record and the
+// operations on it. `probing` (MODE 2, per row) is the caller's.
+template <int MODE>
+struct ArgAcc : ArgRec<MODE> {
+  __device__ __forceinline__ ArgAcc() {
+    this->best = 0;
+    if constexpr (MODE >= 1) this->m = -INFINITY, this->s = 0.f;
+    if constexpr (MODE == 2) this->am = this->px = -INFINITY, this->as = this->pad = 0.f;
+  }
+  __device__ __forceinline__ ArgAcc(const ArgRec<MODE>& r) : ArgRec<MODE>(r) {}
+
+  // columns v0 .. v0 + N - 1, allowed where bits has a 1
+  template <int N>
+  __device__ __forceinline__ void group(const float (&f)[N], uint32_t bits, int v0, bool probing,
+                                        int pb) {
+#pragma unroll
+    for (int j = 0; j < N; ++j)
+      if ((bits >> j) & 1u) this->best = max(this->best, argpack(f[j], v0 + j));
+    if constexpr (MODE >= 1) lse_add_group<N>(this->m, this->s, f, bits);
+    if constexpr (MODE == 2) if (probing) {
+      lse_add_group<N>(this->am, this->as, f, (1u << N) - 1u);
+#pragma unroll
+      for (int j = 0; j < N; ++j)
+        if (v0 + j == pb) this->px = f[j];
+    }
+  }
+
+  // column v (the tail, or a row whose stride keeps vectors unaligned)
+  __device__ __forceinline__ void one(float x, int v, bool ok, bool probing, int pb) {
+    if (ok) {
+      this->best = max(this->best, argpack(x, v));
+      if constexpr (MODE >= 1) lse_add(this->m, this->s, x);
+    }
+    if constexpr (MODE == 2) if (probing) {
+      lse_add(this->am, this->as, x);
+      if (v == pb) this->px = x;
+    }
+  }
+
+  // Folds in the record o. FMA: lse_merge's form for the masked pair (the
+  // all-column pair has one form). get() fetches each field where it is merged:
+  // the field itself, or in the shuffle tree the same field of another lane, so
+  // that a probing row's extra shuffles and sums stay one block.
+  template <bool FMA, class Get>
+  __device__ __forceinline__ void merge(const ArgRec<MODE>& o, bool probing, Get get) {
+    this->best = max(this->best, get(o.best));
+    if constexpr (MODE >= 1) lse_merge<FMA>(this->m, this->s, get(o.m), get(o.s));
+    if constexpr (MODE == 2) if (probing) {
+      lse_merge<false>(this->am, this->as, get(o.am), get(o.as));   // <false> at every site
+      this->px = fmaxf(this->px, get(o.px));
+    }
+  }
+  template <bool FMA>
+  __device__ __forceinline__ void merge(const ArgRec<MODE>& o, bool probing) {
+    merge<FMA>(o, probing, [](auto x) { return x; });
+  }
+
+  __device__ __forceinline__ void finish(int b, bool probing, const int* __restrict__ token_ids,
+                                         int* __restrict__ out_idx, float* __restrict__ out_logprob,
+                                         float* __restrict__ out_probe) const {
+    out_idx[b] = argunpack(this->best, token_ids);
+    if constexpr (MODE >= 1) out_logprob[b] = lse_logprob(this->best, this->m, this->s);
+    if constexpr (MODE == 2)
+      out_probe[b] = lse_probe_logprob(probing, this->px, this->am, this->as);
+  }
+};
+
+__device__ __forceinline__ float arg_load(const bf16_t* p) { return bf2f(*p); }
+__device__ __forceinline__ float arg_load(const float* p) { return *p; }
+__device__ __forceinline__ void arg_load_group(const bf16_t* p, float (&f)[8]) {
+  unpack8(*reinterpret_cast<const uint4*>(p), f);
+}
+__device__ __forceinline__ void arg_load_group(const float* p, float (&f)[4]) {
+  const float4 q = *reinterpret_cast<const float4*>(p);
+  f[0] = q.x, f[1] = q.y, f[2] = q.z, f[3] = q.w;
+}
+
+// SINGLE: gridDim.x == 1 (V <= ARG_CHUNK); the workgroup writes the row's
+// results. Otherwise `part` is the zeroed packed word per row (MODE 0) or the
+// [B, gridDim.x] chunk records.
+template <bool BF16, bool SINGLE, int MODE>
+__global__ __launch_bounds__(ARG_THREADS) void masked_argmax_kernel(
     const void* __restrict__ logits, long long ld, int V, const uint32_t* __restrict__ mask,
     const int* __restrict__ mask_rows, int W, const int* __restrict__ probe,
-    ArgLseProbe* __restrict__ part, const int* __restrict__ token_ids, int* __restrict__ out_idx,
+    ArgRec<MODE>* __restrict__ part, const int* __restrict__ token_ids, int* __restrict__ out_idx,
     float* __restrict__ out_logprob, float* __restrict__ out_probe) {
-  __shared__ ArgLseProbe sred[ARG_THREADS / 64];
+  using T = typename std::conditional<BF16, bf16_t, float>::type;
+  constexpr int N = BF16 ? 8 : 4;           // one 16-byte load
+  __shared__ ArgRec<MODE> sred[ARG_THREADS / 64];
   const int b = blockIdx.y;
   const int v_begin = blockIdx.x * ARG_CHUNK;
   const int v_end = min(V, v_begin + ARG_CHUNK);
   const uint32_t* m = nullptr;
   if (mask) m = mask + (size_t)(mask_rows ? mask_rows[b] : b) * W;
-  const int pb = probe[b];
-  const bool probing = pb >= 0 && pb < V;
-  unsigned long long best = 0;
-  float mx = -INFINITY, sum = 0.f;
-  float amx = -INFINITY, asum = 0.f, px = -INFINITY;
-  if (BF16) {
-    const bf16_t* row = reinterpret_cast<const bf16_t*>(logits) + (size_t)b * ld;
-    for (int v0 = v_begin + threadIdx.x * 8; v0 < v_end; v0 += ARG_THREADS * 8) {
-      if (v0 + 8 <= v_end && (ld % 8 == 0)) {
-        float f[8];
-        unpack8(*reinterpret_cast<const uint4*>(row + v0), f);
-        const uint32_t bits = m ? (m[v0 >> 5] >> (v0 & 31)) & 0xffu : 0xffu;
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          if ((bits >> j) & 1u) best = max(best, argpack(f[j], v0 + j));
-        lse_add_group<8>(mx, sum, f, bits);
-        if (probing) {
-          lse_add_group<8>(amx, asum, f, 0xffu);
-#pragma unroll
-          for (int j = 0; j < 8; ++j)
-            if (v0 + j == pb) px = f[j];
-        }
-      } else {
-        for (int v = v0; v < min(v_end, v0 + 8); ++v) {
-          const bool ok = !m || ((m[v >> 5] >> (v & 31)) & 1u);
-          if (!ok && !probing) continue;
-          const float x = bf2f(row[v]);
-          if (ok) {
-            best = max(best, argpack(x, v));
-            lse_add(mx, sum, x);
-          }
-          if (probing) {
-            lse_add(amx, asum, x);
-            if (v == pb) px = x;
-          }
-        }
-      }
-    }
-  } else {
-    const float* row = reinterpret_cast<const float*>(logits) + (size_t)b * ld;
-    for (int v0 = v_begin + threadIdx.x * 4; v0 < v_end; v0 += ARG_THREADS * 4) {
-      if (v0 + 4 <= v_end && (ld % 4 == 0)) {
-        const float4 f4 = *reinterpret_cast<const float4*>(row + v0);
-        const float f[4] = {f4.x, f4.y, f4.z, f4.w};
-        const uint32_t bits = m ? (m[v0 >> 5] >> (v0 & 31)) & 0xfu : 0xfu;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if ((bits >> j) & 1u) best = max(best, argpack(f[j], v0 + j));
-        lse_add_group<4>(mx, sum, f, bits);
-        if (probing) {
-          lse_add_group<4>(amx, asum, f, 0xfu);
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (v0 + j == pb) px = f[j];
-        }
-      } else {
-        for (int v = v0; v < min(v_end, v0 + 4); ++v) {
-          const bool ok = !m || ((m[v >> 5] >> (v & 31)) & 1u);
-          if (!ok && !probing) continue;
-          const float x = row[v];
-          if (ok) {
-            best = max(best, argpack(x, v));
-            lse_add(mx, sum, x);
-          }
-          if (probing) {
-            lse_add(amx, asum, x);
-            if (v == pb) px = x;
-          }
-        }
+  int pb = -1;
+  if constexpr (MODE == 2) pb = probe[b];
+  const bool probing = pb >= 0 && pb < V;   // false unless MODE 2
+  const T* row = reinterpret_cast<const T*>(logits) + (size_t)b * ld;
+  ArgAcc<MODE> a;
+  for (int v0 = v_begin + threadIdx.x * N; v0 < v_end; v0 += ARG_THREADS * N) {
+    if (v0 + N <= v_end && (ld % N == 0)) {
+      float f[N];
+      arg_load_group(row + v0, f);
+      const uint32_t all = (1u << N) - 1u;
+      a.template group<N>(f, m ? (m[v0 >> 5] >> (v0 & 31)) & all : all, v0, probing, pb);
+    } else {
+      for (int v = v0; v < min(v_end, v0 + N); ++v) {
+        const bool ok = !m || ((m[v >> 5] >> (v & 31)) & 1u);
+        if (ok || probing) a.one(arg_load(row + v), v, ok, probing, pb);
       }
     }
   }
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long other = __shfl_xor(best, o, 64);
-    best = max(best, other);
-    const float m2 = __shfl_xor(mx, o, 64), s2 = __shfl_xor(sum, o, 64);
-    lse_merge(mx, sum, m2, s2);
-    if (probing) {
-      const float am2 = __shfl_xor(amx, o, 64), as2 = __shfl_xor(asum, o, 64);
-      lse_merge(amx, asum, am2, as2);
-      px = fmaxf(px, __shfl_xor(px, o, 64));
-    }
-  }
-  if ((threadIdx.x & 63) == 0)
-    sred[threadIdx.x >> 6] = ArgLseProbe{best, mx, sum, amx, asum, px, 0.f};
+  for (int o = 32; o > 0; o >>= 1)   // shuffle tree: <true>, the masked pair's 2nd product fused
+    a.template merge<true>(a, probing, [o](auto x) { return __shfl_xor(x, o, 64); });
+  if ((threadIdx.x & 63) == 0) sred[threadIdx.x >> 6] = a;
   __syncthreads();
   if (threadIdx.x == 0) {
-    for (int i = 1; i < ARG_THREADS / 64; ++i) {
-      best = max(best, sred[i].best);
-      lse_merge(mx, sum, sred[i].m, sred[i].s);
-      if (probing) {
-        lse_merge(amx, asum, sred[i].am, sred[i].as);
-        px = fmaxf(px, sred[i].px);
-      }
-    }
-    if (SINGLE) {
-      out_idx[b] = argunpack(best, token_ids);
-      out_logprob[b] = lse_logprob(best, mx, sum);
-      out_probe[b] = lse_probe_logprob(probing, px, amx, asum);
-    } else {
-      part[(size_t)b * gridDim.x + blockIdx.x] = ArgLseProbe{best, mx, sum, amx, asum, px, 0.f};
-    }
+    // LDS fold: <true>, as the shuffle tree
+    for (int i = 1; i < ARG_THREADS / 64; ++i) a.template merge<true>(sred[i], probing);
+    if (SINGLE)
+      a.finish(b, probing, token_ids, out_idx, out_logprob, out_probe);
+    else if constexpr (MODE == 0) {
+      if (a.best) atomicMax(&part[b].best, a.best);
+    } else
+      part[(size_t)b * gridDim.x + blockIdx.x] = a;
   }
 }
 
-// one thread per row: the row's chunk records, merged in chunk order
-__global__ void argmax_lse_probe_finalize_kernel(const ArgLseProbe* __restrict__ part, int B,
-                                                 int chunks, int V, const int* __restrict__ probe,
-                                                 const int* __restrict__ token_ids,
-                                                 int* __restrict__ out_idx,
-                                                 float* __restrict__ out_logprob,
-                                                 float* __restrict__ out_probe) {
+// one thread per row: the row's chunk records, merged in chunk order (MODE 0:
+// the one packed word that the atomics left)
+template <int MODE>
+__global__ void argmax_finalize_kernel(
+    const ArgRec<MODE>* __restrict__ part, int B, int chunks, int V, const int* __restrict__ probe,
+    const int* __restrict__ token_ids, int* __restrict__ out_idx, float* __restrict__ out_logprob,
+    float* __restrict__ out_probe) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  const ArgLseProbe* p = part + (size_t)b * chunks;
-  const int pb = probe[b];
+  int pb = -1;
+  if constexpr (MODE == 2) pb = probe[b];
   const bool probing = pb >= 0 && pb < V;
-  unsigned long long best = p[0].best;
-  float mx = p[0].m, sum = p[0].s;
-  float amx = p[0].am, asum = p[0].as, px = p[0].px;
-  for (int c = 1; c < chunks; ++c) {
-    best = max(best, p[c].best);
-    lse_merge(mx, sum, p[c].m, p[c].s);
-    if (probing) {
-      lse_merge(amx, asum, p[c].am, p[c].as);
-      px = fmaxf(px, p[c].px);
-    }
+  const ArgRec<MODE>* p = part + (size_t)b * chunks;
+  ArgAcc<MODE> a(p[0]);
+  for (int c = 1; c < chunks; ++c) a.template merge<false>(p[c], probing);   // chunks: <false>
+  a.finish(b, probing, token_ids, out_idx, out_logprob, out_probe);
+}
+
+// The argument checks and the SINGLE / chunked dispatch of the three entry
+// points; probe, out_logprob and out_probe are null below their mode.
+// workspace (device, 8-byte aligned, only touched when V > ARG_CHUNK):
+// MODE 0: >= B * 8 bytes, zeroed here; MODE 1 / 2: >= B * ceil(V / ARG_CHUNK)
+// * 16 / 32 bytes, no initialisation needed.
+template <int MODE>
+static int masked_argmax(const void* logits, int is_bf16, long long ld, int B, int V,
+                         const uint32_t* mask, const int* mask_rows, int W, const int* probe,
+                         int* out_idx, float* out_logprob, float* out_probe, void* workspace,
+                         const int* token_ids, hipStream_t s) {
+  if (B <= 0) return 0;
+  if (V <= 0 || (mask && W * 32 < V) || !out_idx) return (int)hipErrorInvalidValue;
+  if (MODE >= 1 && (ld < V || !out_logprob)) return (int)hipErrorInvalidValue;
+  if (MODE == 2 && (!probe || !out_probe)) return (int)hipErrorInvalidValue;
+  const int chunks = (V + ARG_CHUNK - 1) / ARG_CHUNK;
+  const bool single = chunks == 1;
+  ArgRec<MODE>* part = (ArgRec<MODE>*)workspace;
+  if (!single && !workspace) return (int)hipErrorInvalidValue;
+  if (MODE == 0 && !single) {
+    hipError_t e = hipMemsetAsync(part, 0, sizeof(ArgRec<0>) * B, s);
+    if (e != hipSuccess) return (int)e;
   }
-  out_idx[b] = argunpack(best, token_ids);
-  out_logprob[b] = lse_logprob(best, mx, sum);
-  out_probe[b] = lse_probe_logprob(probing, px, amx, asum);
+  auto kernel = is_bf16 ? (single ? masked_argmax_kernel<true, true, MODE>
+                                  : masked_argmax_kernel<true, false, MODE>)
+                        : (single ? masked_argmax_kernel<false, true, MODE>
+                                  : masked_argmax_kernel<false, false, MODE>);
+  hipLaunchKernelGGL(kernel, dim3(chunks, B), dim3(ARG_THREADS), 0, s, logits, ld, V, mask,
+                     mask_rows, W, probe, single ? nullptr : part, token_ids, out_idx, out_logprob,
+                     out_probe);
+  hipError_t e = hipGetLastError();
+  if (single || e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(argmax_finalize_kernel<MODE>, dim3((B + 63) / 64), dim3(64), 0, s,
+                     (const ArgRec<MODE>*)part, B, MODE == 0 ? 1 : chunks, V, probe, token_ids,
+                     out_idx, out_logprob, out_probe);
+  return (int)hipGetLastError();
 }
 
-template <bool SINGLE>
-static void launch_masked_argmax_lse_probe(int is_bf16, dim3 grid, hipStream_t s,
-                                           const void* logits, long long ld, int V,
-                                           const uint32_t* mask, const int* mask_rows, int W,
-                                           const int* probe, ArgLseProbe* part,
-                                           const int* token_ids, int* out_idx, float* out_logprob,
-                                           float* out_probe) {
-  if (is_bf16)
-    hipLaunchKernelGGL((masked_argmax_lse_probe_kernel<true, SINGLE>), grid, dim3(ARG_THREADS), 0,
-                       s, logits, ld, V, mask, mask_rows, W, probe, part, token_ids, out_idx,
-                       out_logprob, out_probe);
-  else
-    hipLaunchKernelGGL((masked_argmax_lse_probe_kernel<false, SINGLE>), grid, dim3(ARG_THREADS), 0,
-                       s, logits, ld, V, mask, mask_rows, W, probe, part, token_ids, out_idx,
-                       out_logprob, out_probe);
+// token_ids: null, or int32 [V]; probe: int32 [B] (device)
+extern "C" int loqa_masked_argmax(const void* logits, int is_bf16, long long ld, int B, int V,
+                                  const uint32_t* mask, const int* mask_rows, int W, int* out_idx,
+                                  void* workspace, const int* token_ids, hipStream_t s) {
+  return masked_argmax<0>(logits, is_bf16, ld, B, V, mask, mask_rows, W, nullptr, out_idx, nullptr,
+                          nullptr, workspace, token_ids, s);
 }
-
-// probe: int32 [B] (device); workspace: >= B * ceil(V / ARG_CHUNK) * 32 bytes
-// (device, 8-byte aligned); only touched when V > ARG_CHUNK, and needs no
-// initialisation.
+extern "C" int loqa_masked_argmax_lse(const void* logits, int is_bf16, long long ld, int B, int V,
+                                      const uint32_t* mask, const int* mask_rows, int W,
+                                      int* out_idx, float* out_logprob, void* workspace,
+                                      const int* token_ids, hipStream_t s) {
+  return masked_argmax<1>(logits, is_bf16, ld, B, V, mask, mask_rows, W, nullptr, out_idx,
+                          out_logprob, nullptr, workspace, token_ids, s);
+}
 extern "C" int loqa_masked_argmax_lse_probe(const void* logits, int is_bf16, long long ld, int B,
                                             int V, const uint32_t* mask, const int* mask_rows,
                                             int W, const int* probe, int* out_idx,
                                             float* out_logprob, float* out_probe, void* workspace,
                                             const int* token_ids, hipStream_t s) {
-  if (B <= 0) return 0;
-  if (V <= 0 || ld < V || (mask && W * 32 < V) || !probe || !out_idx || !out_logprob || !out_probe)
-    return (int)hipErrorInvalidValue;
-  if (V <= ARG_CHUNK) {
-    launch_masked_argmax_lse_probe<true>(is_bf16, dim3(1, B), s, logits, ld, V, mask, mask_rows, W,
-                                         probe, nullptr, token_ids, out_idx, out_logprob,
-                                         out_probe);
-    return (int)hipGetLastError();
-  }
-  if (!workspace) return (int)hipErrorInvalidValue;
-  const int chunks = (V + ARG_CHUNK - 1) / ARG_CHUNK;
-  launch_masked_argmax_lse_probe<false>(is_bf16, dim3(chunks, B), s, logits, ld, V, mask,
-                                        mask_rows, W, probe, (ArgLseProbe*)workspace, token_ids,
-                                        out_idx, out_logprob, out_probe);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(argmax_lse_probe_finalize_kernel, dim3((B + 63) / 64), dim3(64), 0, s,
-                     (const ArgLseProbe*)workspace, B, chunks, V, probe, token_ids, out_idx,
-                     out_logprob, out_probe);
-  return (int)hipGetLastError();
+  return masked_argmax<2>(logits, is_bf16, ld, B, V, mask, mask_rows, W, probe, out_idx,
+                          out_logprob, out_probe, workspace, token_ids, s);
 }
 
 // ------------------------------------------------- pipelined decode: step I/O
@@ -907,16 +693,24 @@ __global__ __launch_bounds__(256) void step_fetch_kernel(int* __restrict__ d32,
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n64; i += gridDim.x * 256) d64[i] = src64[i];
 }
 
-__global__ __launch_bounds__(256) void step_publish_kernel(const int* __restrict__ out, int n,
-                                                          int* __restrict__ res, int stride,
-                                                          int nres, int* __restrict__ ctr,
-                                                          const int* __restrict__ row_slot,
-                                                          int* __restrict__ last_tok) {
+// The step's tokens, and NLP (0, 1 or 2) f32 values per sequence (the token
+// log-probabilities; the probed log-probability): slot (ctr % nres) of a second
+// pinned ring (f32, row stride lp_stride) is a row of planes, lp[i] at [i] and
+// lp2[i] at [plane + i]. Every store precedes the fence and the counter store
+// that order the tokens.
+template <int NLP>
+__global__ __launch_bounds__(256) void step_publish_kernel(
+    const int* __restrict__ out, const float* __restrict__ lp, const float* __restrict__ lp2, int n,
+    int* __restrict__ res, int stride, float* __restrict__ res_lp, int lp_stride, int plane,
+    int nres, int* __restrict__ ctr, const int* __restrict__ row_slot, int* __restrict__ last_tok) {
   const int c = ctr[0];
   int* dst = res + (size_t)(c % nres) * stride;
+  float* dst_lp = NLP ? res_lp + (size_t)(c % nres) * lp_stride : nullptr;
   for (int i = threadIdx.x; i < n; i += 256) {
     const int v = out[i];
     dst[i] = v;
+    if (NLP >= 1) dst_lp[i] = lp[i];
+    if (NLP == 2) dst_lp[plane + i] = lp2[i];
     last_tok[row_slot[i]] = v;     // padding rows write the trash slot
   }
   __syncthreads();
@@ -925,53 +719,6 @@ __global__ __launch_bounds__(256) void step_publish_kernel(const int* __restrict
     // wrap at 2 * nres (a common multiple of the 2 staging slots and the nres
     // result slots; the host's step number wraps the same way), so the counter
     // never overflows on a long-running hub
-    __hip_atomic_store(ctr, (c + 1) % (2 * nres), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
-// step_publish_kernel plus the step's token log-probabilities: lp[i] goes to
-// slot (ctr % nres) of a second pinned ring (f32, row stride lp_stride), before
-// the fence and the counter store that order the tokens.
-__global__ __launch_bounds__(256) void step_publish_lp_kernel(
-    const int* __restrict__ out, const float* __restrict__ lp, int n, int* __restrict__ res,
-    int stride, float* __restrict__ res_lp, int lp_stride, int nres, int* __restrict__ ctr,
-    const int* __restrict__ row_slot, int* __restrict__ last_tok) {
-  const int c = ctr[0];
-  int* dst = res + (size_t)(c % nres) * stride;
-  float* dst_lp = res_lp + (size_t)(c % nres) * lp_stride;
-  for (int i = threadIdx.x; i < n; i += 256) {
-    const int v = out[i];
-    dst[i] = v;
-    dst_lp[i] = lp[i];
-    last_tok[row_slot[i]] = v;     // padding rows write the trash slot
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __threadfence_system();
-    __hip_atomic_store(ctr, (c + 1) % (2 * nres), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
-// step_publish_lp_kernel with two f32 values per sequence: slot (ctr % nres) of
-// the f32 ring is a row of two planes, lp[i] at [i] and lp2[i] at [plane + i],
-// both written before the fence and the counter store.
-__global__ __launch_bounds__(256) void step_publish_lp2_kernel(
-    const int* __restrict__ out, const float* __restrict__ lp, const float* __restrict__ lp2, int n,
-    int* __restrict__ res, int stride, float* __restrict__ res_lp, int lp_stride, int plane,
-    int nres, int* __restrict__ ctr, const int* __restrict__ row_slot, int* __restrict__ last_tok) {
-  const int c = ctr[0];
-  int* dst = res + (size_t)(c % nres) * stride;
-  float* dst_lp = res_lp + (size_t)(c % nres) * lp_stride;
-  for (int i = threadIdx.x; i < n; i += 256) {
-    const int v = out[i];
-    dst[i] = v;
-    dst_lp[i] = lp[i];
-    dst_lp[plane + i] = lp2[i];
-    last_tok[row_slot[i]] = v;     // padding rows write the trash slot
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __threadfence_system();
     __hip_atomic_store(ctr, (c + 1) % (2 * nres), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
@@ -991,35 +738,37 @@ extern "C" int loqa_step_fetch(void* d32, const void* h32, int n32, int stride32
   return (int)hipGetLastError();
 }
 
-extern "C" int loqa_step_publish(const int* out, int n, void* res, int stride, int nres, int* ctr,
-                                 const int* row_slot, int* last_tok, hipStream_t s) {
+// res_lp rows: lp_stride floats, lp at [0, n), lp2 at [plane, plane + n)
+template <int NLP>
+static int step_publish(const int* out, const float* lp, const float* lp2, int n, void* res,
+                        int stride, void* res_lp, int lp_stride, int plane, int nres, int* ctr,
+                        const int* row_slot, int* last_tok, hipStream_t s) {
   if (n < 0 || n > stride || nres < 1) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(step_publish_kernel, dim3(1), dim3(256), 0, s, out, n, (int*)res, stride, nres, ctr,
-                     row_slot, last_tok);
+  if (NLP >= 1 && (!lp || !res_lp)) return (int)hipErrorInvalidValue;
+  if (NLP == 1 && n > lp_stride) return (int)hipErrorInvalidValue;
+  if (NLP == 2 && (!lp2 || n > plane || plane > lp_stride - n)) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(step_publish_kernel<NLP>, dim3(1), dim3(256), 0, s, out, lp, lp2, n, (int*)res,
+                     stride, (float*)res_lp, lp_stride, plane, nres, ctr, row_slot, last_tok);
   return (int)hipGetLastError();
 }
 
+extern "C" int loqa_step_publish(const int* out, int n, void* res, int stride, int nres, int* ctr,
+                                 const int* row_slot, int* last_tok, hipStream_t s) {
+  return step_publish<0>(out, nullptr, nullptr, n, res, stride, nullptr, 0, 0, nres, ctr, row_slot,
+                         last_tok, s);
+}
 extern "C" int loqa_step_publish_lp(const int* out, const float* lp, int n, void* res, int stride,
                                     void* res_lp, int lp_stride, int nres, int* ctr,
                                     const int* row_slot, int* last_tok, hipStream_t s) {
-  if (n < 0 || n > stride || n > lp_stride || nres < 1 || !lp || !res_lp)
-    return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(step_publish_lp_kernel, dim3(1), dim3(256), 0, s, out, lp, n, (int*)res, stride,
-                     (float*)res_lp, lp_stride, nres, ctr, row_slot, last_tok);
-  return (int)hipGetLastError();
+  return step_publish<1>(out, lp, nullptr, n, res, stride, res_lp, lp_stride, 0, nres, ctr,
+                         row_slot, last_tok, s);
 }
-
-// res_lp rows: lp_stride floats, lp at [0, n), lp2 at [plane, plane + n)
 extern "C" int loqa_step_publish_lp2(const int* out, const float* lp, const float* lp2, int n,
                                      void* res, int stride, void* res_lp, int lp_stride, int plane,
                                      int nres, int* ctr, const int* row_slot, int* last_tok,
                                      hipStream_t s) {
-  if (n < 0 || n > stride || n > plane || plane > lp_stride - n || nres < 1 || !lp || !lp2 ||
-      !res_lp)
-    return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(step_publish_lp2_kernel, dim3(1), dim3(256), 0, s, out, lp, lp2, n, (int*)res,
-                     stride, (float*)res_lp, lp_stride, plane, nres, ctr, row_slot, last_tok);
-  return (int)hipGetLastError();
+  return step_publish<2>(out, lp, lp2, n, res, stride, res_lp, lp_stride, plane, nres, ctr,
+                         row_slot, last_tok, s);
 }
 
 // ---------------------------------------------------------------------------

@@ -260,20 +260,20 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_q: torch.Ten
 
 
 # ----------------------------------------------------------------- sampling
-def masked_argmax(logits: torch.Tensor, mask: torch.Tensor | None = None,
-                  mask_rows: torch.Tensor | None = None,
-                  token_ids: torch.Tensor | None = None) -> torch.Tensor:
-    """argmax over tokens allowed by a packed uint32 bitmask (bit v%32 of word
-    v//32). ``mask_rows`` optionally maps each logits row to a mask-table row.
-    ``token_ids`` (int32 [V], ascending): the columns are a gathered subset of
-    the vocabulary (the compact sampling head; ``mask`` is in column order) and
-    the result is ``token_ids[column]``. Returns int32 [B] (-1 if nothing is
-    allowed)."""
+ARG_CHUNK = 8192    # tokens per workgroup of the argmax kernel (elementwise.hip)
+
+
+def _check_token_ids(logits: torch.Tensor, token_ids: torch.Tensor | None) -> None:
     if token_ids is not None:
         assert token_ids.dtype == torch.int32 and token_ids.is_contiguous()
         assert token_ids.numel() >= logits.shape[-1] and token_ids.device == logits.device
-    if not _gpu(logits):
-        return ref.masked_argmax(logits, mask, mask_rows, token_ids)
+
+
+def _argmax_args(logits: torch.Tensor, mask, mask_rows, n_float: int, ws_words: int):
+    """GPU-side checks and buffers shared by the three argmax ops: the leading
+    arguments of their entry points, the int32 [B] result, ``n_float`` float32
+    [B] results, and the workspace of a row wider than one chunk (``ws_words``
+    int64 per row and chunk; 0: one per row), written before it is read."""
     assert logits.dim() == 2 and logits.stride(-1) == 1
     B, V = logits.shape
     W = 0
@@ -288,14 +288,30 @@ def masked_argmax(logits: torch.Tensor, mask: torch.Tensor | None = None,
     is_bf16 = logits.dtype == torch.bfloat16
     assert is_bf16 or logits.dtype == torch.float32
     out = torch.empty(B, dtype=torch.int32, device=logits.device)
-    ws = torch.empty(B, dtype=torch.int64, device=logits.device)
-    check(kernels().loqa_masked_argmax(ptr(logits), int(is_bf16), logits.stride(0), B, V,
-                                       ptr(mask), ptr(mask_rows), W, ptr(out), ptr(ws),
-                                       ptr(token_ids), stream_ptr(logits)), "masked_argmax")
+    floats = [torch.empty(B, dtype=torch.float32, device=logits.device) for _ in range(n_float)]
+    chunks = (V + ARG_CHUNK - 1) // ARG_CHUNK
+    ws = torch.empty(B * chunks * ws_words if ws_words else B, dtype=torch.int64,
+                     device=logits.device) if chunks > 1 else None
+    head = (ptr(logits), int(is_bf16), logits.stride(0), B, V, ptr(mask), ptr(mask_rows), W)
+    return head, out, floats, ws
+
+
+def masked_argmax(logits: torch.Tensor, mask: torch.Tensor | None = None,
+                  mask_rows: torch.Tensor | None = None,
+                  token_ids: torch.Tensor | None = None) -> torch.Tensor:
+    """argmax over tokens allowed by a packed uint32 bitmask (bit v%32 of word
+    v//32). ``mask_rows`` optionally maps each logits row to a mask-table row.
+    ``token_ids`` (int32 [V], ascending): the columns are a gathered subset of
+    the vocabulary (the compact sampling head; ``mask`` is in column order) and
+    the result is ``token_ids[column]``. Returns int32 [B] (-1 if nothing is
+    allowed)."""
+    _check_token_ids(logits, token_ids)
+    if not _gpu(logits):
+        return ref.masked_argmax(logits, mask, mask_rows, token_ids)
+    head, out, _, ws = _argmax_args(logits, mask, mask_rows, 0, 0)
+    check(kernels().loqa_masked_argmax(*head, ptr(out), ptr(ws), ptr(token_ids),
+                                       stream_ptr(logits)), "masked_argmax")
     return out
-
-
-ARG_CHUNK = 8192    # tokens per workgroup of the argmax kernels (elementwise.hip)
 
 
 def masked_argmax_logprob(logits: torch.Tensor, mask: torch.Tensor | None = None,
@@ -308,33 +324,12 @@ def masked_argmax_logprob(logits: torch.Tensor, mask: torch.Tensor | None = None
     allowed gives (-1, -inf), a row whose only allowed token wins gives 0.0.
     One launch for V <= 8192, else per-chunk partials and a fixed-order merge
     (no memset, no atomics: bitwise repeatable)."""
-    if token_ids is not None:
-        assert token_ids.dtype == torch.int32 and token_ids.is_contiguous()
-        assert token_ids.numel() >= logits.shape[-1] and token_ids.device == logits.device
+    _check_token_ids(logits, token_ids)
     if not _gpu(logits):
         return ref.masked_argmax_logprob(logits, mask, mask_rows, token_ids)
-    assert logits.dim() == 2 and logits.stride(-1) == 1
-    B, V = logits.shape
-    W = 0
-    if mask is not None:
-        assert mask.dtype == torch.int32 and mask.is_contiguous()
-        W = mask.shape[-1]
-        assert W * 32 >= V
-        if mask_rows is not None:
-            assert mask_rows.dtype == torch.int32 and mask_rows.numel() == B
-        else:
-            assert mask.shape[0] >= B
-    is_bf16 = logits.dtype == torch.bfloat16
-    assert is_bf16 or logits.dtype == torch.float32
-    out = torch.empty(B, dtype=torch.int32, device=logits.device)
-    lp = torch.empty(B, dtype=torch.float32, device=logits.device)
-    chunks = (V + ARG_CHUNK - 1) // ARG_CHUNK
-    # 16-byte chunk records [B, chunks] (written before they are read)
-    ws = torch.empty(B * chunks * 2, dtype=torch.int64, device=logits.device) if chunks > 1 else None
-    check(kernels().loqa_masked_argmax_lse(ptr(logits), int(is_bf16), logits.stride(0), B, V,
-                                           ptr(mask), ptr(mask_rows), W, ptr(out), ptr(lp),
-                                           ptr(ws), ptr(token_ids), stream_ptr(logits)),
-          "masked_argmax_lse")
+    head, out, (lp,), ws = _argmax_args(logits, mask, mask_rows, 1, 2)   # 16-byte records
+    check(kernels().loqa_masked_argmax_lse(*head, ptr(out), ptr(lp), ptr(ws), ptr(token_ids),
+                                           stream_ptr(logits)), "masked_argmax_lse")
     return out, lp
 
 
@@ -350,9 +345,7 @@ def masked_argmax_logprob_probe(logits: torch.Tensor, mask: torch.Tensor | None,
     second sum, a row of -inf only gives -inf. A column >= V is a ValueError
     when ``probe`` is a host tensor; on the device such a row counts as < 0.
     Returns (int32 [B], float32 [B], float32 [B])."""
-    if token_ids is not None:
-        assert token_ids.dtype == torch.int32 and token_ids.is_contiguous()
-        assert token_ids.numel() >= logits.shape[-1] and token_ids.device == logits.device
+    _check_token_ids(logits, token_ids)
     assert logits.dim() == 2 and logits.stride(-1) == 1
     B, V = logits.shape
     assert probe.dtype == torch.int32 and probe.is_contiguous() and probe.numel() == B
@@ -361,27 +354,10 @@ def masked_argmax_logprob_probe(logits: torch.Tensor, mask: torch.Tensor | None,
         raise ValueError(f"probe column {int(probe.max())} is outside the {V} logits")
     if not _gpu(logits):
         return ref.masked_argmax_logprob_probe(logits, mask, mask_rows, probe, token_ids)
-    W = 0
-    if mask is not None:
-        assert mask.dtype == torch.int32 and mask.is_contiguous()
-        W = mask.shape[-1]
-        assert W * 32 >= V
-        if mask_rows is not None:
-            assert mask_rows.dtype == torch.int32 and mask_rows.numel() == B
-        else:
-            assert mask.shape[0] >= B
-    is_bf16 = logits.dtype == torch.bfloat16
-    assert is_bf16 or logits.dtype == torch.float32
-    out = torch.empty(B, dtype=torch.int32, device=logits.device)
-    lp = torch.empty(B, dtype=torch.float32, device=logits.device)
-    plp = torch.empty(B, dtype=torch.float32, device=logits.device)
-    chunks = (V + ARG_CHUNK - 1) // ARG_CHUNK
-    # 32-byte chunk records [B, chunks] (written before they are read)
-    ws = torch.empty(B * chunks * 4, dtype=torch.int64, device=logits.device) if chunks > 1 else None
+    head, out, (lp, plp), ws = _argmax_args(logits, mask, mask_rows, 2, 4)   # 32-byte records
     check(kernels().loqa_masked_argmax_lse_probe(
-        ptr(logits), int(is_bf16), logits.stride(0), B, V, ptr(mask), ptr(mask_rows), W,
-        ptr(probe), ptr(out), ptr(lp), ptr(plp), ptr(ws), ptr(token_ids), stream_ptr(logits)),
-        "masked_argmax_lse_probe")
+        *head, ptr(probe), ptr(out), ptr(lp), ptr(plp), ptr(ws), ptr(token_ids),
+        stream_ptr(logits)), "masked_argmax_lse_probe")
     return out, lp, plp
 
 

@@ -1,12 +1,17 @@
 """A/B of the Whisper sampling tail with and without token log-probabilities
 (``STTEngine(token_logprobs=True)``, ``HUB_STT_CONFIDENCE=acoustic``), on a GPU.
 
-``op``: ``ops.masked_argmax`` against ``ops.masked_argmax_logprob`` at the
-Whisper step shape: f32 logits, 16 rows x 51866 columns of a [16, 51904]
-lm_head output, one shared suppress-mask row. Each side is a captured graph of
-``--ops`` back-to-back calls (launch overhead off the host), replayed
-alternately ``--rounds`` times between device events; per call: median, min,
-max over the rounds. The indices of both sides must be equal.
+``op``: ``ops.masked_argmax`` against ``ops.masked_argmax_logprob`` and
+``ops.masked_argmax_logprob_probe`` (a probe column on every row), one shared
+mask row, at ``--shape``: ``whisper`` (the Whisper step: f32, 16 rows x 51866
+columns of a [16, 51904] lm_head output), ``llama`` (bf16, 16 x 128256, the
+Llama vocabulary) or ``compact`` (bf16, 16 x 4096 with ``token_ids``: the
+compact head's single-workgroup path) - between them both dtypes, and the
+chunked and the single-workgroup form of the argmax kernel. Each side is a
+captured graph of ``--ops`` back-to-back calls (launch overhead off the
+host), replayed alternately ``--rounds`` times between device events; per
+call: median, min, max over the rounds. The indices of all sides, and the
+log-probabilities of the last two, must be equal.
 
 ``step``: whole decode steps of a Whisper engine (free decoding, ``--batch``
 utterances, captured step graphs, synchronous steps), feature on against off on
@@ -30,17 +35,29 @@ from loqa_hub_amd.models.configs import whisper_config  # noqa: E402
 from loqa_hub_amd.ops.reference import pack_mask  # noqa: E402
 
 
-def bench_op(n_ops: int, rounds: int) -> dict:
+# --shape: (dtype, rows, columns, row stride, token_ids)
+SHAPES = {
+    "whisper": (torch.float32, 16, 51866, 51904, False),    # multi-chunk, f32
+    "llama": (torch.bfloat16, 16, 128256, 128256, False),   # multi-chunk, bf16
+    "compact": (torch.bfloat16, 16, 4096, 4096, True),      # one workgroup per row, token_ids
+}
+
+
+def bench_op(n_ops: int, rounds: int, shape: str = "whisper") -> dict:
     dev = torch.device("cuda", 0)
-    B, V, ld = 16, 51866, 51904
+    dtype, B, V, ld, with_ids = SHAPES[shape]
     g = torch.Generator().manual_seed(0)
-    buf = (torch.randn(B, ld, generator=g) * 4).to(dev)
+    buf = (torch.randn(B, ld, generator=g) * 4).to(dtype).to(dev)
     logits = buf[:, :V]
     allowed = torch.rand(1, V, generator=g) < 0.9
     mask = pack_mask(allowed).to(dev)
     rows = torch.zeros(B, dtype=torch.int32, device=dev)
-    sides = {"masked_argmax": lambda: ops.masked_argmax(logits, mask, rows),
-             "masked_argmax_logprob": lambda: ops.masked_argmax_logprob(logits, mask, rows)}
+    ids = (torch.arange(V, dtype=torch.int32) * 3).to(dev) if with_ids else None
+    probe = torch.full((B,), V // 2, dtype=torch.int32, device=dev)   # every row probes
+    sides = {"masked_argmax": lambda: ops.masked_argmax(logits, mask, rows, ids),
+             "masked_argmax_logprob": lambda: ops.masked_argmax_logprob(logits, mask, rows, ids),
+             "masked_argmax_logprob_probe":
+                 lambda: ops.masked_argmax_logprob_probe(logits, mask, rows, probe, ids)}
     graphs, outs = {}, {}
     s = torch.cuda.Stream(dev)
     with torch.cuda.stream(s):
@@ -53,8 +70,9 @@ def bench_op(n_ops: int, rounds: int) -> dict:
                 for _ in range(n_ops):
                     fn()
             graphs[name] = gr
-        idx_new = outs["masked_argmax_logprob"][0]
-        assert torch.equal(outs["masked_argmax"], idx_new)
+        assert torch.equal(outs["masked_argmax"], outs["masked_argmax_logprob"][0])
+        for x, y in zip(outs["masked_argmax_logprob"], outs["masked_argmax_logprob_probe"]):
+            assert torch.equal(x, y)
         times = {k: [] for k in sides}
         for name in sides:                       # warm both graphs
             graphs[name].replay()
@@ -103,6 +121,7 @@ if __name__ == "__main__":
     ap.add_argument("what", choices=["op", "step", "both"], nargs="?", default="both")
     ap.add_argument("--ops", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=15)
+    ap.add_argument("--shape", choices=sorted(SHAPES), default="whisper")
     ap.add_argument("--model", default="whisper-large-v3")
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--new-tokens", type=int, default=48)
@@ -110,7 +129,7 @@ if __name__ == "__main__":
     assert torch.cuda.is_available(), "needs a GPU"
     res = {}
     if a.what in ("op", "both"):
-        res["op"] = bench_op(a.ops, a.rounds)
+        res["op"] = {"shape": a.shape, **bench_op(a.ops, a.rounds, a.shape)}
     if a.what in ("step", "both"):
         res["step"] = bench_step(a.model, a.batch, a.new_tokens, a.rounds)
     print(json.dumps(res))

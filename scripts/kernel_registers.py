@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Registers, occupancy and LDS of the hot decode kernels, from the compiler's
 resource remarks (``hipcc -Rpass-analysis=kernel-resource-usage``, device-only
-compile of ``gemm_skinny.hip``, ``gemm_skinny_fp8.hip``, ``gemm_skinny_mxfp4.hip`` and
-``attn_decode.hip`` for gfx950; ~3 min).
+compile of ``gemm_skinny.hip``, ``gemm_skinny_fp8.hip``, ``gemm_skinny_mxfp4.hip``,
+``attn_decode.hip`` and ``elementwise.hip`` for gfx950; ~3 min).
 
 The question it answers: can a Whisper decoder wave sit beside an LLM decode
 GEMM workgroup on the same CU (one 512-entry VGPR + AGPR file per SIMD lane)?
@@ -42,6 +42,13 @@ LABELS = {
     "attn_decode_kernel<128, 0, 4, 2>": "Llama decode attention (D 128)",
     "attn_decode_kernel<64, 0, 4, 2>": "Whisper self / cross attention (D 64)",
 }
+# the sampling tail's argmax (elementwise.hip): <bf16, one workgroup per row, mode>
+LABELS.update({
+    f"masked_argmax_kernel<{str(bf).lower()}, {str(single).lower()}, {mode}>":
+        f"argmax{('', ' + logprob', ' + logprob + probe')[mode]}, {'bf16' if bf else 'f32'}, "
+        f"{'V <= 8192' if single else 'chunked'}"
+    for mode in (0, 1, 2) for bf in (True, False) for single in (True, False)})
+LABELS.update({f"argmax_finalize_kernel<{mode}>": f"argmax finalize, mode {mode}" for mode in (0, 1, 2)})
 PAT = {"V": r"VGPRs: (\d+)", "A": r"AGPRs: (\d+)", "occ": r"Occupancy \[waves/SIMD\]: (\d+)",
        "LDS": r"LDS Size \[bytes/block\]: (\d+)", "spill": r"VGPRs Spill: (\d+)"}
 
@@ -63,7 +70,8 @@ def main() -> int:
           "-Rpass-analysis=kernel-resource-usage; scripts/kernel_registers.py)")
     print("# V = arch VGPRs, A = AGPRs (one 512-entry file per SIMD lane); occ = waves per SIMD "
           "of the kernel alone")
-    for src in ("gemm_skinny.hip", "gemm_skinny_fp8.hip", "gemm_skinny_mxfp4.hip", "attn_decode.hip"):
+    for src in ("gemm_skinny.hip", "gemm_skinny_fp8.hip", "gemm_skinny_mxfp4.hip", "attn_decode.hip",
+                "elementwise.hip"):
         blocks = re.split(r"remark: Function Name: ", remarks(src))[1:]
         names = [b.split(" ")[0] for b in blocks]
         dem = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True,
@@ -71,11 +79,10 @@ def main() -> int:
         for b, d in zip(blocks, dem):
             d = (d.replace("skinny_fused_fp8_kernel", "SF8").replace("skinny_fused_mxfp4_kernel", "SF4")
                  .replace("skinny_fused_kernel", "SF")
-                 .replace("(FusedArgs)", "")
-                 .replace("(AttnDecArgs)", "").replace("void ", "").strip())
+                 .replace("void ", "").split("(")[0].strip())
             if d in LABELS:
                 vals = {k: (m.group(1) if (m := re.search(p, b)) else "?") for k, p in PAT.items()}
-                print(f"{LABELS[d]:38s} {d:34s} " + " ".join(f"{k}={v}" for k, v in vals.items()))
+                print(f"{LABELS[d]:44s} {d:38s} " + " ".join(f"{k}={v}" for k, v in vals.items()))
     return 0
 
 

@@ -3,7 +3,7 @@ kernels between the 8B lm_head GEMM and the step's step_publish (the other
 decoder's kernels can interleave, so the most common sequence is reported)."""
 import csv, sys, statistics as st
 from collections import Counter
-KEEP = ("masked_argmax", "argmax_unpack", "fillBuffer", "step_publish")
+KEEP = ("masked_argmax", "argmax_finalize", "fillBuffer", "step_publish")
 rows = []
 with open(sys.argv[1]) as f:
     for r in csv.DictReader(f):

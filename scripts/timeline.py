@@ -8,7 +8,7 @@ from collections import defaultdict
 
 def family(name: str) -> str:
     if "skinny_gemm" in name or "slab_" in name or "attn_decode" in name or "masked_argmax" in name \
-            or "argmax_unpack" in name:
+            or "argmax_finalize" in name:
         return "llm_decode"
     if "attn_fwd_kernel<128" in name or "rmsnorm" in name or "rope_kv_append" in name or \
             "silu_mul" in name:

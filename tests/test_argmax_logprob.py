@@ -1,6 +1,6 @@
 """``ops.masked_argmax_logprob``: the masked argmax and the log-probability of
 the token it selects (``csrc/kernels/elementwise.hip``,
-``masked_argmax_lse_kernel`` + ``argmax_lse_finalize_kernel``; on the CPU
+``masked_argmax_kernel<.., 1>`` + ``argmax_finalize_kernel<1>``; on the CPU
 ``ops.reference.masked_argmax_logprob``).
 
 **Index.** ``torch.equal`` to ``ops.masked_argmax`` on the same inputs: winner,

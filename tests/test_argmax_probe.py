@@ -1,7 +1,7 @@
 """``ops.masked_argmax_logprob_probe``: ``ops.masked_argmax_logprob`` plus the
 log-softmax of one fixed column per row BEFORE the mask
-(``csrc/kernels/elementwise.hip``, ``masked_argmax_lse_probe_kernel`` +
-``argmax_lse_probe_finalize_kernel``; on the CPU
+(``csrc/kernels/elementwise.hip``, ``masked_argmax_kernel<.., 2>`` +
+``argmax_finalize_kernel<2>``; on the CPU
 ``ops.reference.masked_argmax_logprob_probe``).
 
 **Bitwise against the sibling.** ``idx`` and ``lp`` equal

@@ -163,7 +163,7 @@ def test_decode_buckets(n):
 
 def test_ring_constants():
     # step_fetch_kernel picks the staging row with (counter & 1), and
-    # step_publish_kernel wraps the counter at 2 * nres
+    # step_publish_kernel<NLP> wraps the counter at 2 * nres
     assert StepIO.STAGE_SLOTS == 2 and StepIO.WRAP == 2 * StepIO.RES_SLOTS
     assert StepIO.WRAP % StepIO.STAGE_SLOTS == 0 and StepIO.WRAP % StepIO.RES_SLOTS == 0
     StepIO.check_depth(StepIO.RES_SLOTS - 1)
