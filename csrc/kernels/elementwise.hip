@@ -324,8 +324,8 @@ extern "C" int loqa_pcm16_f32_pad(const void* pcm, float* out, const long long* 
 }
 
 // --------------------------------------------------- K15 grammar-masked argmax
-// One row scan in three modes behind loqa_masked_argmax (MODE 0), _lse (1) and
-// _lse_probe (2). The modes share the arithmetic and its order, so a higher
+// One row scan in four modes behind loqa_masked_argmax (MODE 0), _lse (1),
+// _lse_probe (2) and _ts (3). The modes share the arithmetic and its order, so a higher
 // mode returns the lower modes' results bit for bit.
 // logits: [B, V] (bf16 if is_bf16 else f32), row stride ld elements.
 // mask: [*, W] uint32 bitmask (bit v%32 of word v/32 = token v allowed), or null;
@@ -452,6 +452,78 @@ template <> struct ArgRec<2> {
   float am, as;     // all columns (probing rows)
   float px, pad;    // the probed logit, -inf where this record does not hold it
 };
+template <> struct ArgRec<3> : ArgRec<2> {
+  unsigned long long tbest;   // the best allowed timestamp column
+  float tm, tsum;             // allowed timestamp columns (ruled rows)
+};
+
+// MODE 3: Whisper's timestamp rules as a state machine beside the scan. ctl[b]:
+// 0 = rules off (the row is MODE 2's, the state untouched), 1 = the window's
+// first sampled token, 2 = continue from state[row_slot[b]]. The state word is
+// (last + 1) << 2 | f_last << 1 | f_pen: the last timestamp index sampled in the
+// window (-1: none), "the last token was a timestamp", "the one before it was
+// (or fewer than two tokens are sampled)". Timestamp token k = column
+// ts_begin + k, k < ts_count; columns below eot are text, [eot, ts_begin) are
+// specials that only the mask governs.
+struct TsArgs {
+  const int* ctl;
+  int* state;
+  const int* row_slot;
+  int slots, ts_begin, ts_count, eot, max_initial;
+};
+
+// What a row may select: columns [x_from, x_to) where the mask has a bit, and
+// the timestamp columns [t_from, t_to) whatever their mask bits. A rule-off row
+// is [0, V) and no timestamp class, so it scans exactly as MODE 2 does.
+struct TsRow {
+  int ctl, slot, last, f_last;
+  int x_from, x_to, t_from, t_to;
+};
+
+__device__ __forceinline__ TsRow ts_row(const TsArgs& t, int b, int V) {
+  TsRow r;
+  r.ctl = t.ctl[b];
+  r.slot = t.row_slot[b];
+  if (r.ctl < 1 || r.ctl > 2 || r.slot < 0 || r.slot >= t.slots) r.ctl = 0;
+  r.last = -1, r.f_last = 0;
+  r.x_from = 0, r.x_to = V, r.t_from = r.t_to = 0;
+  if (r.ctl == 0) return r;
+  r.x_to = min(V, t.ts_begin);
+  int lo = 0, hi = t.max_initial;
+  if (r.ctl == 1) {
+    r.x_from = r.x_to;                          // a window opens with a timestamp
+  } else {
+    const int w = t.state[r.slot];
+    r.last = (w >> 2) - 1, r.f_last = (w >> 1) & 1;
+    const bool f_pen = w & 1;
+    hi = t.ts_count - 1;
+    lo = r.last < 0 ? 0 : (r.f_last && !f_pen) ? r.last : r.last + 1;
+    if (r.f_last && f_pen) lo = hi + 1;                       // a pair is closed: text next
+    if (r.f_last && !f_pen) r.x_from = min(t.eot, r.x_to);    // a lone one: a timestamp or EOT
+  }
+  lo = min(lo, t.ts_count), hi = min(hi, t.ts_count - 1);
+  r.t_from = min(V, t.ts_begin + lo);
+  r.t_to = max(r.t_from, min(V, t.ts_begin + hi + 1));
+  return r;
+}
+
+// bit j: column v0 + j lies in [from, to); N <= 8 columns
+__device__ __forceinline__ uint32_t range_bits(int v0, int N, int from, int to) {
+  const int a = min(max(from - v0, 0), N), e = min(max(to - v0, 0), N);
+  return e > a ? ((1u << e) - 1u) & ~((1u << a) - 1u) : 0u;
+}
+
+// Whisper's mass rule in f32, its roundings spelled out: with lA / lT the
+// logsumexp of every allowed column / of the allowed timestamps and xt the best
+// allowed logit below ts_begin, the timestamps win when their log-probability
+// mass lT - lA exceeds the best text token's xt - lA. Nothing allowed below
+// ts_begin: they win; no timestamp allowed, or an exact tie: they do not.
+__device__ __forceinline__ bool ts_fires(bool any_x, bool any_t, float xt, float mA, float sA,
+                                         float tm, float tsum) {
+#pragma clang fp contract(off)
+  const float lA = mA + logf(sA), lT = tm + logf(tsum);
+  return any_t && (!any_x || (lT - lA) > (xt - lA));
+}
 
 // The running state of a thread, a wave, a chunk or a row: a record and the
 // operations on it. `probing` (MODE 2, per row) is the caller's.
@@ -460,7 +532,8 @@ struct ArgAcc : ArgRec<MODE> {
   __device__ __forceinline__ ArgAcc() {
     this->best = 0;
     if constexpr (MODE >= 1) this->m = -INFINITY, this->s = 0.f;
-    if constexpr (MODE == 2) this->am = this->px = -INFINITY, this->as = this->pad = 0.f;
+    if constexpr (MODE >= 2) this->am = this->px = -INFINITY, this->as = this->pad = 0.f;
+    if constexpr (MODE == 3) this->tbest = 0, this->tm = -INFINITY, this->tsum = 0.f;
   }
   __device__ __forceinline__ ArgAcc(const ArgRec<MODE>& r) : ArgRec<MODE>(r) {}
 
@@ -472,7 +545,7 @@ struct ArgAcc : ArgRec<MODE> {
     for (int j = 0; j < N; ++j)
       if ((bits >> j) & 1u) this->best = max(this->best, argpack(f[j], v0 + j));
     if constexpr (MODE >= 1) lse_add_group<N>(this->m, this->s, f, bits);
-    if constexpr (MODE == 2) if (probing) {
+    if constexpr (MODE >= 2) if (probing) {
       lse_add_group<N>(this->am, this->as, f, (1u << N) - 1u);
 #pragma unroll
       for (int j = 0; j < N; ++j)
@@ -486,28 +559,46 @@ struct ArgAcc : ArgRec<MODE> {
       this->best = max(this->best, argpack(x, v));
       if constexpr (MODE >= 1) lse_add(this->m, this->s, x);
     }
-    if constexpr (MODE == 2) if (probing) {
+    if constexpr (MODE >= 2) if (probing) {
       lse_add(this->am, this->as, x);
       if (v == pb) this->px = x;
     }
   }
 
+  // MODE 3, a ruled row: the allowed timestamp columns of a group / one column
+  template <int N>
+  __device__ __forceinline__ void tgroup(const float (&f)[N], uint32_t bits, int v0) {
+#pragma unroll
+    for (int j = 0; j < N; ++j)
+      if ((bits >> j) & 1u) this->tbest = max(this->tbest, argpack(f[j], v0 + j));
+    lse_add_group<N>(this->tm, this->tsum, f, bits);
+  }
+  __device__ __forceinline__ void tone(float x, int v) {
+    this->tbest = max(this->tbest, argpack(x, v));
+    lse_add(this->tm, this->tsum, x);
+  }
+
   // Folds in the record o. FMA: lse_merge's form for the masked pair (the
   // all-column pair has one form). get() fetches each field where it is merged:
   // the field itself, or in the shuffle tree the same field of another lane, so
-  // that a probing row's extra shuffles and sums stay one block.
+  // that a probing row's extra shuffles and sums stay one block. `ruled` (MODE
+  // 3, per row): the timestamp class is merged too, in the masked pair's form.
   template <bool FMA, class Get>
-  __device__ __forceinline__ void merge(const ArgRec<MODE>& o, bool probing, Get get) {
+  __device__ __forceinline__ void merge(const ArgRec<MODE>& o, bool probing, bool ruled, Get get) {
     this->best = max(this->best, get(o.best));
     if constexpr (MODE >= 1) lse_merge<FMA>(this->m, this->s, get(o.m), get(o.s));
-    if constexpr (MODE == 2) if (probing) {
+    if constexpr (MODE >= 2) if (probing) {
       lse_merge<false>(this->am, this->as, get(o.am), get(o.as));   // <false> at every site
       this->px = fmaxf(this->px, get(o.px));
     }
+    if constexpr (MODE == 3) if (ruled) {
+      this->tbest = max(this->tbest, get(o.tbest));
+      lse_merge<FMA>(this->tm, this->tsum, get(o.tm), get(o.tsum));
+    }
   }
   template <bool FMA>
-  __device__ __forceinline__ void merge(const ArgRec<MODE>& o, bool probing) {
-    merge<FMA>(o, probing, [](auto x) { return x; });
+  __device__ __forceinline__ void merge(const ArgRec<MODE>& o, bool probing, bool ruled) {
+    merge<FMA>(o, probing, ruled, [](auto x) { return x; });
   }
 
   __device__ __forceinline__ void finish(int b, bool probing, const int* __restrict__ token_ids,
@@ -515,8 +606,39 @@ struct ArgAcc : ArgRec<MODE> {
                                          float* __restrict__ out_probe) const {
     out_idx[b] = argunpack(this->best, token_ids);
     if constexpr (MODE >= 1) out_logprob[b] = lse_logprob(this->best, this->m, this->s);
-    if constexpr (MODE == 2)
+    if constexpr (MODE >= 2)
       out_probe[b] = lse_probe_logprob(probing, this->px, this->am, this->as);
+  }
+
+  // MODE 3: a rule-off row finishes as MODE 2 does. A ruled row decides between
+  // its two classes by the mass rule; the winner's log-probability is over the
+  // timestamps alone when they win (Whisper masks the text then), else over
+  // every allowed column. It then writes the row's next state word.
+  __device__ __forceinline__ void finish(int b, bool probing, const TsRow& r, const TsArgs& t,
+                                         int* __restrict__ out_idx, float* __restrict__ out_logprob,
+                                         float* __restrict__ out_probe) const {
+    if (r.ctl == 0) {
+      finish(b, probing, nullptr, out_idx, out_logprob, out_probe);
+      return;
+    }
+    out_probe[b] = lse_probe_logprob(probing, this->px, this->am, this->as);
+    float mA = this->m, sA = this->s;
+    lse_merge<false>(mA, sA, this->tm, this->tsum);
+    const bool fire = ts_fires(this->best != 0, this->tbest != 0, this->m, mA, sA, this->tm,
+                               this->tsum);
+    const int col = argunpack(fire ? this->tbest : this->best, nullptr);
+    out_idx[b] = col;
+    if (col < 0) {                     // nothing allowed: the state stays
+      out_logprob[b] = -INFINITY;
+      return;
+    }
+    if (fire)
+      out_logprob[b] = lse_logprob(this->tbest, this->tm, this->tsum);
+    else                               // x[winner] = m, the maximum below ts_begin
+      out_logprob[b] = this->m != -INFINITY ? (this->m - mA) - logf(sA) : -INFINITY;
+    const int f_last = col >= t.ts_begin;
+    const int last = f_last ? col - t.ts_begin : r.last;
+    t.state[r.slot] = ((last + 1) << 2) | (f_last << 1) | (r.ctl == 1 ? 1 : r.f_last);
   }
 };
 
@@ -533,12 +655,14 @@ __device__ __forceinline__ void arg_load_group(const float* p, float (&f)[4]) {
 // SINGLE: gridDim.x == 1 (V <= ARG_CHUNK); the workgroup writes the row's
 // results. Otherwise `part` is the zeroed packed word per row (MODE 0) or the
 // [B, gridDim.x] chunk records.
-template <bool BF16, bool SINGLE, int MODE>
+// TS: empty below MODE 3 (the kernel's arguments are the lower modes' own), else TsArgs.
+template <bool BF16, bool SINGLE, int MODE, class... TS>
 __global__ __launch_bounds__(ARG_THREADS) void masked_argmax_kernel(
     const void* __restrict__ logits, long long ld, int V, const uint32_t* __restrict__ mask,
     const int* __restrict__ mask_rows, int W, const int* __restrict__ probe,
     ArgRec<MODE>* __restrict__ part, const int* __restrict__ token_ids, int* __restrict__ out_idx,
-    float* __restrict__ out_logprob, float* __restrict__ out_probe) {
+    float* __restrict__ out_logprob, float* __restrict__ out_probe, TS... ts) {
+  static_assert(sizeof...(TS) == (MODE == 3 ? 1 : 0), "MODE 3 takes one TsArgs");
   using T = typename std::conditional<BF16, bf16_t, float>::type;
   constexpr int N = BF16 ? 8 : 4;           // one 16-byte load
   __shared__ ArgRec<MODE> sred[ARG_THREADS / 64];
@@ -548,8 +672,12 @@ __global__ __launch_bounds__(ARG_THREADS) void masked_argmax_kernel(
   const uint32_t* m = nullptr;
   if (mask) m = mask + (size_t)(mask_rows ? mask_rows[b] : b) * W;
   int pb = -1;
-  if constexpr (MODE == 2) pb = probe[b];
-  const bool probing = pb >= 0 && pb < V;   // false unless MODE 2
+  if constexpr (MODE >= 2) pb = probe[b];
+  const bool probing = pb >= 0 && pb < V;   // false below MODE 2
+  TsRow tr;
+  if constexpr (MODE == 3) tr = ts_row(ts..., b, V);
+  bool ruled = false;                       // per row too; false below MODE 3
+  if constexpr (MODE == 3) ruled = tr.ctl != 0;
   const T* row = reinterpret_cast<const T*>(logits) + (size_t)b * ld;
   ArgAcc<MODE> a;
   for (int v0 = v_begin + threadIdx.x * N; v0 < v_end; v0 += ARG_THREADS * N) {
@@ -557,23 +685,40 @@ __global__ __launch_bounds__(ARG_THREADS) void masked_argmax_kernel(
       float f[N];
       arg_load_group(row + v0, f);
       const uint32_t all = (1u << N) - 1u;
-      a.template group<N>(f, m ? (m[v0 >> 5] >> (v0 & 31)) & all : all, v0, probing, pb);
+      uint32_t bits = m ? (m[v0 >> 5] >> (v0 & 31)) & all : all;
+      if constexpr (MODE == 3) if (ruled) bits &= range_bits(v0, N, tr.x_from, tr.x_to);
+      a.template group<N>(f, bits, v0, probing, pb);
+      if constexpr (MODE == 3) if (ruled) {
+        const uint32_t tbits = range_bits(v0, N, tr.t_from, tr.t_to);
+        if (tbits) a.template tgroup<N>(f, tbits, v0);
+      }
     } else {
       for (int v = v0; v < min(v_end, v0 + N); ++v) {
-        const bool ok = !m || ((m[v >> 5] >> (v & 31)) & 1u);
-        if (ok || probing) a.one(arg_load(row + v), v, ok, probing, pb);
+        bool ok = !m || ((m[v >> 5] >> (v & 31)) & 1u);
+        bool tok = false;
+        if constexpr (MODE == 3) if (ruled) {
+          ok = ok && v >= tr.x_from && v < tr.x_to;
+          tok = v >= tr.t_from && v < tr.t_to;
+        }
+        if (ok || probing || tok) {
+          const float x = arg_load(row + v);
+          a.one(x, v, ok, probing, pb);
+          if constexpr (MODE == 3) if (tok) a.tone(x, v);
+        }
       }
     }
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1)   // shuffle tree: <true>, the masked pair's 2nd product fused
-    a.template merge<true>(a, probing, [o](auto x) { return __shfl_xor(x, o, 64); });
+    a.template merge<true>(a, probing, ruled, [o](auto x) { return __shfl_xor(x, o, 64); });
   if ((threadIdx.x & 63) == 0) sred[threadIdx.x >> 6] = a;
   __syncthreads();
   if (threadIdx.x == 0) {
     // LDS fold: <true>, as the shuffle tree
-    for (int i = 1; i < ARG_THREADS / 64; ++i) a.template merge<true>(sred[i], probing);
-    if (SINGLE)
+    for (int i = 1; i < ARG_THREADS / 64; ++i) a.template merge<true>(sred[i], probing, ruled);
+    if constexpr (SINGLE && MODE == 3)   // every thread read the old state before the barrier
+      a.finish(b, probing, tr, ts..., out_idx, out_logprob, out_probe);
+    else if (SINGLE)
       a.finish(b, probing, token_ids, out_idx, out_logprob, out_probe);
     else if constexpr (MODE == 0) {
       if (a.best) atomicMax(&part[b].best, a.best);
@@ -584,36 +729,44 @@ __global__ __launch_bounds__(ARG_THREADS) void masked_argmax_kernel(
 
 // one thread per row: the row's chunk records, merged in chunk order (MODE 0:
 // the one packed word that the atomics left)
-template <int MODE>
+template <int MODE, class... TS>
 __global__ void argmax_finalize_kernel(
     const ArgRec<MODE>* __restrict__ part, int B, int chunks, int V, const int* __restrict__ probe,
     const int* __restrict__ token_ids, int* __restrict__ out_idx, float* __restrict__ out_logprob,
-    float* __restrict__ out_probe) {
+    float* __restrict__ out_probe, TS... ts) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   int pb = -1;
-  if constexpr (MODE == 2) pb = probe[b];
+  if constexpr (MODE >= 2) pb = probe[b];
   const bool probing = pb >= 0 && pb < V;
+  TsRow tr;
+  if constexpr (MODE == 3) tr = ts_row(ts..., b, V);
+  bool ruled = false;
+  if constexpr (MODE == 3) ruled = tr.ctl != 0;
   const ArgRec<MODE>* p = part + (size_t)b * chunks;
   ArgAcc<MODE> a(p[0]);
-  for (int c = 1; c < chunks; ++c) a.template merge<false>(p[c], probing);   // chunks: <false>
-  a.finish(b, probing, token_ids, out_idx, out_logprob, out_probe);
+  for (int c = 1; c < chunks; ++c) a.template merge<false>(p[c], probing, ruled);   // chunks: <false>
+  // MODE 3: the scan launch has finished, so no workgroup still reads the old state
+  if constexpr (MODE == 3)
+    a.finish(b, probing, tr, ts..., out_idx, out_logprob, out_probe);
+  else
+    a.finish(b, probing, token_ids, out_idx, out_logprob, out_probe);
 }
 
 // The argument checks and the SINGLE / chunked dispatch of the three entry
 // points; probe, out_logprob and out_probe are null below their mode.
 // workspace (device, 8-byte aligned, only touched when V > ARG_CHUNK):
 // MODE 0: >= B * 8 bytes, zeroed here; MODE 1 / 2: >= B * ceil(V / ARG_CHUNK)
-// * 16 / 32 bytes, no initialisation needed.
-template <int MODE>
+// * 16 / 32 bytes (MODE 3: 48), no initialisation needed.
+template <int MODE, class... TS>
 static int masked_argmax(const void* logits, int is_bf16, long long ld, int B, int V,
                          const uint32_t* mask, const int* mask_rows, int W, const int* probe,
                          int* out_idx, float* out_logprob, float* out_probe, void* workspace,
-                         const int* token_ids, hipStream_t s) {
+                         const int* token_ids, hipStream_t s, TS... ts) {
   if (B <= 0) return 0;
   if (V <= 0 || (mask && W * 32 < V) || !out_idx) return (int)hipErrorInvalidValue;
   if (MODE >= 1 && (ld < V || !out_logprob)) return (int)hipErrorInvalidValue;
-  if (MODE == 2 && (!probe || !out_probe)) return (int)hipErrorInvalidValue;
+  if (MODE >= 2 && (!probe || !out_probe)) return (int)hipErrorInvalidValue;
   const int chunks = (V + ARG_CHUNK - 1) / ARG_CHUNK;
   const bool single = chunks == 1;
   ArgRec<MODE>* part = (ArgRec<MODE>*)workspace;
@@ -622,18 +775,18 @@ static int masked_argmax(const void* logits, int is_bf16, long long ld, int B, i
     hipError_t e = hipMemsetAsync(part, 0, sizeof(ArgRec<0>) * B, s);
     if (e != hipSuccess) return (int)e;
   }
-  auto kernel = is_bf16 ? (single ? masked_argmax_kernel<true, true, MODE>
-                                  : masked_argmax_kernel<true, false, MODE>)
-                        : (single ? masked_argmax_kernel<false, true, MODE>
-                                  : masked_argmax_kernel<false, false, MODE>);
+  auto kernel = is_bf16 ? (single ? masked_argmax_kernel<true, true, MODE, TS...>
+                                  : masked_argmax_kernel<true, false, MODE, TS...>)
+                        : (single ? masked_argmax_kernel<false, true, MODE, TS...>
+                                  : masked_argmax_kernel<false, false, MODE, TS...>);
   hipLaunchKernelGGL(kernel, dim3(chunks, B), dim3(ARG_THREADS), 0, s, logits, ld, V, mask,
                      mask_rows, W, probe, single ? nullptr : part, token_ids, out_idx, out_logprob,
-                     out_probe);
+                     out_probe, ts...);
   hipError_t e = hipGetLastError();
   if (single || e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(argmax_finalize_kernel<MODE>, dim3((B + 63) / 64), dim3(64), 0, s,
+  hipLaunchKernelGGL((argmax_finalize_kernel<MODE, TS...>), dim3((B + 63) / 64), dim3(64), 0, s,
                      (const ArgRec<MODE>*)part, B, MODE == 0 ? 1 : chunks, V, probe, token_ids,
-                     out_idx, out_logprob, out_probe);
+                     out_idx, out_logprob, out_probe, ts...);
   return (int)hipGetLastError();
 }
 
@@ -658,6 +811,24 @@ extern "C" int loqa_masked_argmax_lse_probe(const void* logits, int is_bf16, lon
                                             const int* token_ids, hipStream_t s) {
   return masked_argmax<2>(logits, is_bf16, ld, B, V, mask, mask_rows, W, probe, out_idx,
                           out_logprob, out_probe, workspace, token_ids, s);
+}
+
+// MODE 3 (see TsArgs): ts_ctl, row_slot: int32 [B]; ts_state: int32 [slots],
+// read and written in place by the ruled rows, whose slots must differ. The
+// columns are the vocabulary itself (no token_ids).
+extern "C" int loqa_masked_argmax_ts(const void* logits, int is_bf16, long long ld, int B, int V,
+                                     const uint32_t* mask, const int* mask_rows, int W,
+                                     const int* probe, const int* ts_ctl, int* ts_state,
+                                     const int* row_slot, int slots, int ts_begin, int ts_count,
+                                     int eot, int max_initial, int* out_idx, float* out_logprob,
+                                     float* out_probe, void* workspace, hipStream_t s) {
+  if (B > 0 && (!ts_ctl || !ts_state || !row_slot || slots <= 0 || ts_count <= 0 || eot < 0 ||
+                eot > ts_begin || ts_begin > V - ts_count || max_initial < 0))
+    return (int)hipErrorInvalidValue;
+  const TsArgs t{ts_ctl, ts_state, row_slot, slots, ts_begin, ts_count, eot,
+                 min(max_initial, ts_count - 1)};
+  return masked_argmax<3>(logits, is_bf16, ld, B, V, mask, mask_rows, W, probe, out_idx,
+                          out_logprob, out_probe, workspace, nullptr, s, t);
 }
 
 // ------------------------------------------------- pipelined decode: step I/O

@@ -225,6 +225,12 @@ class GPUConfig:
     stt_no_speech: str = "off"        # off | on
     stt_no_speech_threshold: float = 0.6
     stt_logprob_threshold: float = -1.0
+    # Whisper's default decoding mode on the gpu backend: "segment" drops
+    # <|notimestamps|> from the prompt, samples under the timestamp rules and
+    # reports (start, end, text) segments; a window's first timestamp is at
+    # most stt_max_initial_timestamp seconds
+    stt_timestamps: str = "off"       # off | segment
+    stt_max_initial_timestamp: float = 1.0
     # relay audio: "fixed" (every chunk is 16 kHz, AudioChunk.sample_rate is
     # ignored: the reference's behaviour) or "relay" (the stream's own rate, one
     # of AUDIO_SAMPLE_RATES; the gpu STT resamples it to 16 kHz on the device,
@@ -373,6 +379,15 @@ class Config:
         if not self.gpu.stt_logprob_threshold <= 0.0:
             raise ConfigError("HUB_STT_LOGPROB_THRESHOLD must be <= 0: "
                               f"{self.gpu.stt_logprob_threshold}")
+        if self.gpu.stt_timestamps not in ("off", "segment"):
+            raise ConfigError("invalid HUB_STT_TIMESTAMPS (off | segment): "
+                              f"{self.gpu.stt_timestamps}")
+        if self.gpu.stt_timestamps == "segment" and self.gpu.stt_backend != "gpu":
+            raise ConfigError("HUB_STT_TIMESTAMPS=segment needs HUB_STT_BACKEND=gpu: "
+                              f"{self.gpu.stt_backend}")
+        if not 0.0 <= self.gpu.stt_max_initial_timestamp <= 30.0:
+            raise ConfigError("HUB_STT_MAX_INITIAL_TIMESTAMP must be in [0, 30] seconds: "
+                              f"{self.gpu.stt_max_initial_timestamp}")
         for c in self.gpu.stt_languages:
             if not re.fullmatch(r"[a-z]{2,3}", c):
                 raise ConfigError(f"invalid HUB_STT_LANGUAGES entry: {c!r}")
@@ -506,6 +521,8 @@ def load(env=None) -> Config:
             stt_no_speech=env_str(e, "off", "HUB_STT_NO_SPEECH").strip().lower(),
             stt_no_speech_threshold=_strict_float(e, 0.6, "HUB_STT_NO_SPEECH_THRESHOLD"),
             stt_logprob_threshold=_strict_float(e, -1.0, "HUB_STT_LOGPROB_THRESHOLD"),
+            stt_timestamps=env_str(e, "off", "HUB_STT_TIMESTAMPS").strip().lower(),
+            stt_max_initial_timestamp=_strict_float(e, 1.0, "HUB_STT_MAX_INITIAL_TIMESTAMP"),
             audio_input_rate=env_str(e, "fixed", "HUB_AUDIO_INPUT_RATE").lower(),
             tts_sample_rate=_tts_sample_rate(e),
             tts_backend=env_str(e, "gpu", "HUB_TTS_BACKEND"),

@@ -54,6 +54,10 @@ class PipelineJob:
     error: str = ""
     stt_failed: bool = False
     no_speech: bool = False                 # every window fell to the STT engine's no-speech rule
+    # STT engine with timestamps (else None): (start_s, end_s, text) segments in
+    # utterance time, and the windows whose last segment was left open
+    segments: list | None = None
+    open_segments: list | None = None
     llm_steps: int = 0                      # decode steps the intent parse sampled in
     t: dict = field(default_factory=dict)   # stage timestamps (perf_counter)
 
@@ -146,7 +150,9 @@ class VoicePipeline:
         j.transcription = to_transcription_result(
             r.text, r.avg_logprob if self.stt_acoustic is not False else None,
             self.stt_confirm_below, language=r.language,
-            language_prob=r.language_prob, no_speech_prob=r.no_speech_prob)
+            language_prob=r.language_prob, no_speech_prob=r.no_speech_prob,
+            segments=r.segments, speech_start_s=r.speech_start_s, speech_end_s=r.speech_end_s)
+        j.segments, j.open_segments = r.segments, r.open_segments
         j.no_speech = r.gated_windows > 0 and r.gated_windows == r.windows
 
     def build_request(self, j: PipelineJob) -> GenRequest | None:

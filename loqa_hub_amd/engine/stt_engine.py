@@ -29,7 +29,9 @@ from ..utils.tracing import tracer
 from .batching import join_futures, plan_step
 from .kv_cache import PagedKVCache
 from .step_io import StepIO, StepLayout, decode_buckets, fill_meta, step_shapes, to_device
-from .tokenizer import SyntheticTokenizer, SyntheticWhisperTokenizer, get_tokenizer
+from .stt_segments import cut_window, text_tokens, utterance_segments
+from .tokenizer import (SyntheticTimestampTokenizer, SyntheticTokenizer, SyntheticWhisperTokenizer,
+                        get_tokenizer)
 
 log = logging.getLogger("loqa.stt")
 
@@ -89,6 +91,15 @@ class STTRequest:
     language_prob: float | None = None
     no_speech_probs: list[float] = field(default_factory=list)
     no_speech_prob: float | None = None
+    # STTEngine(timestamps=True), free decoding (None with the feature off):
+    # ``segments`` = (start_s, end_s, text) in utterance time (window w adds
+    # 30 w s; ends clamped to the utterance's duration), the first segment's
+    # start and the last one's end, and the windows whose last segment never got
+    # its closing timestamp (cut by the window edge, EOT or the token limit)
+    segments: list | None = None
+    speech_start_s: float | None = None
+    speech_end_s: float | None = None
+    open_segments: list | None = None
     seq_id: int = -1
     t_done: float = 0.0
     t_enc0: float = 0.0               # encoder start / end, decoder start (perf_counter)
@@ -137,7 +148,8 @@ class STTEngine:
                  contended_tuning: bool = False, tokenizer=None, language: str = "en",
                  token_logprobs: bool = False, sot_probe: bool = False,
                  languages: list[str] | None = None, no_speech: bool = False,
-                 no_speech_threshold: float = 0.6, logprob_threshold: float = -1.0):
+                 no_speech_threshold: float = 0.6, logprob_threshold: float = -1.0,
+                 timestamps: bool = False, max_initial_timestamp: float = 1.0):
         self.cfg = cfg
         # language "auto" (or empty, as the reference passes an empty
         # STT_LANGUAGE through): the language is the argmax over the candidate
@@ -156,7 +168,14 @@ class STTEngine:
         self.sot_probe = bool(sot_probe) or self.auto_language or self.no_speech
         # every step also returns the log-softmax (after the suppress mask) of
         # the token it samples (ops.masked_argmax_logprob); off: ops.masked_argmax
-        token_logprobs = bool(token_logprobs) or self.sot_probe
+        # timestamps: the prompt drops <|notimestamps|> and every step samples
+        # under Whisper's timestamp rules (ops.masked_argmax_timestamps), their
+        # state per cross-attention slot in ``ts_state`` on the device
+        self.timestamps = bool(timestamps)
+        # the engine stages per-sequence sampling fields (mask_row, probe, with
+        # timestamps ts_ctl) and a step returns three results
+        self.row_fields = self.sot_probe or self.timestamps
+        token_logprobs = bool(token_logprobs) or self.row_fields
         self.token_logprobs = token_logprobs
         self.device = torch.device(device)
         if self.device.type == "cuda" and self.device.index is None:
@@ -173,12 +192,24 @@ class STTEngine:
         self.tok = tokenizer or get_tokenizer(cfg.vocab_size)
         if self.sot_probe and isinstance(self.tok, SyntheticTokenizer):
             self.tok = SyntheticWhisperTokenizer(self.tok)
+        if self.timestamps:
+            if isinstance(self.tok, (SyntheticTokenizer, SyntheticWhisperTokenizer)):
+                self.tok = SyntheticTimestampTokenizer(self.tok)
+            if not hasattr(self.tok, "timestamp_tokens"):
+                raise ValueError("STT timestamps: the tokenizer has no timestamp tokens")
+            self.ts_begin, self.ts_count = self.tok.timestamp_tokens()
+            mit = float(max_initial_timestamp)
+            if not 0.0 <= mit <= 30.0:
+                raise ValueError(f"max_initial_timestamp {mit} s is outside [0, 30]")
+            self.max_initial = min(self.ts_count - 1, int(round(mit / 0.02)))
         self.step_fields = self.STEP_FIELDS
         if self.sot_probe:
             self._init_probe(language, languages)
             language = self.lang_codes[0]      # placeholder in ``sot``: fed per request
+        if self.row_fields:
             i = self.STEP_FIELDS.index("src")
-            self.step_fields = self.STEP_FIELDS[:i] + ("mask_row", "probe") + self.STEP_FIELDS[i:]
+            extra = ("mask_row", "probe") + (("ts_ctl",) if self.timestamps else ())
+            self.step_fields = self.STEP_FIELDS[:i] + extra + self.STEP_FIELDS[i:]
         # start-of-transcript prompt; the language token follows STT_LANGUAGE
         # (the reference passes it to its STT service)
         try:
@@ -188,7 +219,11 @@ class STTEngine:
                              "tokenizer (a multilingual Whisper tokenizer.json has one)") from None
         self.sot = [self.tok.token_id("<|startoftranscript|>"), lang,
                     self.tok.token_id("<|transcribe|>"), self.tok.token_id("<|notimestamps|>")]
+        if self.timestamps:
+            self.sot.pop()      # Whisper's default mode: timestamps on
         self.eot = self.tok.token_id("<|endoftext|>")
+        if self.timestamps and not self.eot < self.ts_begin:
+            raise ValueError("STT timestamps: <|endoftext|> must lie below the timestamp tokens")
         self.n_prompt_tokens_per_step = len(self.sot)
         try:
             self.sop = self.tok.token_id("<|startofprev|>")
@@ -199,16 +234,20 @@ class STTEngine:
         # reference's STT service decodes); one packed mask row for every
         # sequence. The synthetic tokenizer of the random-init weights: none.
         self._sup = self._sup_rows = None
-        if self.sot_probe:
+        if self.row_fields:
             # a table of two rows, picked per sequence by the step's ``mask_row``
             # field: 0 = the suppress mask (all ones for the synthetic tokenizer),
-            # 1 = the candidate language tokens (the SOT step)
+            # 1 = the candidate language tokens (the SOT step; a timestamps
+            # engine that does not probe has row 0 alone)
             from ..ops.reference import pack_mask
             row0 = self.tok.sampling_mask(keep=(self.eot,)) if hasattr(self.tok, "sampling_mask") \
                 else torch.ones(cfg.vocab_size, dtype=torch.bool)
-            row1 = torch.zeros(cfg.vocab_size, dtype=torch.bool)
-            row1[self.lang_ids] = True
-            self._sup = pack_mask(torch.stack([row0, row1])).to(self.device)
+            rows = [row0]
+            if self.sot_probe:
+                row1 = torch.zeros(cfg.vocab_size, dtype=torch.bool)
+                row1[self.lang_ids] = True
+                rows.append(row1)
+            self._sup = pack_mask(torch.stack(rows)).to(self.device)
         elif hasattr(self.tok, "sampling_mask"):
             from ..ops.reference import pack_mask
             self._sup = pack_mask(self.tok.sampling_mask(keep=(self.eot,))[None]).to(self.device)
@@ -229,6 +268,11 @@ class STTEngine:
             self.stats.update(logprob_tokens=0, logprob_sum=0.0)
         if self.sot_probe:
             self.stats.update(no_speech_windows=0, no_speech_utterances=0, languages={})
+        if self.timestamps:
+            self.stats.update(timestamp_segments=0, open_segments=0)
+            # the rule state of every cross-attention slot (+ a trash slot, the
+            # last, for padding rows), beside ``last_tok``
+            self.ts_state = torch.zeros(max_batch + 1, dtype=torch.int32, device=self.device)
         self.max_batch = max_batch
         self.fast_decode = fast_decode
         # fused-epilogue decoder GEMMs (8 launches per layer) for Mpad <= 64
@@ -274,7 +318,7 @@ class STTEngine:
             b_max = next((b for b in self.SEQ_BUCKETS if b >= max_batch), self.SEQ_BUCKETS[-1])
             self.last_tok = torch.zeros(max_batch + 1, dtype=torch.int32, device=self.device)
             self.io = StepIO(self.device, self._layout(b_max, ops.MPADS[-1]), self.last_tok,
-                             logprobs=2 if self.sot_probe else token_logprobs)
+                             logprobs=2 if self.row_fields else token_logprobs)
         # two decoder steps in flight (the host prepares step j+1 while step j
         # runs); LOQA_STT_PIPELINE=0: one synchronous step at a time
         self.pipelined = self.use_graphs and os.environ.get("LOQA_STT_PIPELINE", "1") != "0"
@@ -310,8 +354,9 @@ class STTEngine:
 
     def _layout(self, B_pad: int, T_pad: int) -> StepLayout:
         """``step_layout`` of this engine (a probing one stages two more
-        per-sequence fields, ``mask_row`` and ``probe``)."""
-        if not self.sot_probe:
+        per-sequence fields, ``mask_row`` and ``probe``; a timestamps one those
+        and ``ts_ctl``)."""
+        if not self.row_fields:
             return self.step_layout(B_pad, T_pad, self.max_blocks)
         return StepLayout(step_shapes(self.step_fields, B_pad, T_pad, self.max_blocks),
                           max(16, ops.mpad_for(B_pad)))
@@ -470,12 +515,14 @@ class STTEngine:
 
     def _host_meta(self, live: list[STTRequest], B_pad: int, T_pad: int,
                    out: dict | None = None, feeds: list | None = None,
-                   sot: list | None = None) -> tuple[int, dict]:
+                   sot: list | None = None, ts_ctl: list | None = None) -> tuple[int, dict]:
         """Host metadata of one step feeding ``feeds`` (default: every
         request's ``feed``); ``out`` = preallocated views (a staging row) to
         fill in place and return. ``sot`` (probing engine): the requests whose
         feed ends in SOT this step (default: ``sot_pending`` and the whole
-        remaining prompt fed)."""
+        remaining prompt fed). ``ts_ctl`` (timestamps engine): the rows' rule
+        control words (default: ``_ts_ctl`` of a step that feeds every request's
+        whole remaining feed)."""
         T_enc = self.cfg.n_audio_ctx
         if feeds is None:
             feeds = [r.feed for r in live]
@@ -490,7 +537,7 @@ class STTEngine:
         enc_starts[n:] = 0
         enc_lens[:n] = T_enc
         enc_lens[n:] = 0
-        if self.sot_probe:
+        if self.row_fields:
             if sot is None:
                 sot = [r.sot_pending and len(f) == len(r.feed) for r, f in zip(live, feeds)]
             if out is None:
@@ -501,7 +548,28 @@ class STTEngine:
             mask_row[n:] = 0
             probe[:n] = [self.nospeech if x else -1 for x in sot]
             probe[n:] = -1
+        if self.timestamps:
+            if ts_ctl is None:
+                ts_ctl = [self._ts_ctl(r, len(f) < len(r.feed)) for r, f in zip(live, feeds)]
+            if out is None:
+                # an eager step: the graphs' callers stage ``row_slot`` themselves
+                host["ts_ctl"] = np.zeros(B_pad, np.int32)
+                host["row_slot"] = np.full(B_pad, self.max_batch, np.int32)
+                host["row_slot"][:n] = [r.slot for r in live]
+            host["ts_ctl"][:n] = ts_ctl
+            host["ts_ctl"][n:] = 0
         return max([len(f) for f in feeds] + [1]), host
+
+    def _ts_ctl(self, r: STTRequest, partial: bool = False) -> int:
+        """The timestamp-rule control word of ``r``'s next step, from what the
+        host knows without seeing tokens: 0 = rules off (a prompt chunk whose
+        logits are discarded - ``partial``: more of the prompt follows -, the SOT
+        probe step, every step of a teacher-forced window: its targets carry no
+        timestamps and the sampled token is not the one fed), 1 = the step that
+        feeds the window's last prompt token, 2 = every later step."""
+        if partial or r.sot_pending or r.target is not None:
+            return 0
+        return 1 if not r.tokens else 2
 
     def _dev(self, host: dict, dst: dict | None = None) -> dict:
         return to_device(host, self.device, dst)
@@ -523,15 +591,22 @@ class STTEngine:
         """``_argmax``; a probing engine: (tokens, log-probabilities, probed
         log-probabilities) under each sequence's mask row, the probe read from
         the step's ``probe`` field."""
-        if not self.sot_probe:
+        if not self.row_fields:
             return self._argmax(logits)
         B = logits.shape[0]
+        if self.timestamps:
+            # the same three results under Whisper's timestamp rules: the rows'
+            # ``ts_ctl`` switches them on, their state is ``ts_state[row_slot]``
+            return ops.masked_argmax_timestamps(
+                logits, self._sup, dev["mask_row"][:B], dev["probe"][:B], dev["ts_ctl"][:B],
+                self.ts_state, dev["row_slot"][:B], self.ts_begin, self.ts_count, self.eot,
+                self.max_initial)
         return ops.masked_argmax_logprob_probe(logits, self._sup, dev["mask_row"][:B],
                                                dev["probe"][:B])
 
     def _host(self, res, B: int | None = None):
         """A step's device result (``_sample``) as numpy, cut to B rows."""
-        if self.sot_probe:
+        if self.row_fields:
             return tuple(x[:B].cpu().numpy() for x in res)
         if self.token_logprobs:
             return res[0][:B].cpu().numpy(), res[1][:B].cpu().numpy()
@@ -619,18 +694,21 @@ class STTEngine:
             for b in range(1, min(self.ENC_GRAPH_MAX, self.max_batch) + 1):
                 self._enc_graph(b)
                 n += 1
-        buckets = decode_buckets(self.SEQ_BUCKETS, self.max_batch, self.step_tokens, len(self.sot),
-                                 self.SPLIT_KEYS, self.cfg.n_text_ctx)
+        # a timestamps engine's prompt is one token shorter (a graph's max_q
+        # follows it); its bucket set is that of the full prompt all the same
+        buckets = decode_buckets(self.SEQ_BUCKETS, self.max_batch, self.step_tokens,
+                                 len(self.sot) + int(self.timestamps), self.SPLIT_KEYS,
+                                 self.cfg.n_text_ctx)
         for b, t, c in buckets:
             self._graph(b, t, c)
         self._graphs_frozen = True
         return n + len(buckets)
 
-    def _step(self, live: list[STTRequest], sot: list | None = None):
+    def _step(self, live: list[STTRequest], sot: list | None = None, ts_ctl: list | None = None):
         """One decoder step for every live request (its ``feed`` tokens): the
         sampled tokens, with ``token_logprobs`` (tokens, log-probabilities), a
-        probing engine (tokens, log-probabilities, probed log-probabilities).
-        ``sot``: see ``_host_meta``."""
+        probing or timestamps engine (tokens, log-probabilities, probed
+        log-probabilities). ``sot``, ``ts_ctl``: see ``_host_meta``."""
         B = len(live)
         T = sum(len(r.feed) for r in live)
         if self.fast_decode:
@@ -642,9 +720,11 @@ class STTEngine:
                 t0 = time.perf_counter()
                 g = self._graph(B_pad, T_pad, C)
                 hb = self.io.stage(g)
-                self._host_meta(live, B_pad, T_pad, out=hb, sot=sot)
+                self._host_meta(live, B_pad, T_pad, out=hb, sot=sot, ts_ctl=ts_ctl)
                 hb["src"].fill(-1)
                 hb["row_slot"].fill(self.io.trash)
+                if self.timestamps:      # the rows' rule state (and last_tok) slots
+                    hb["row_slot"][:B] = [r.slot for r in live]
                 t1 = time.perf_counter()
                 rslot = self.io.replay(g)
                 torch.cuda.current_stream(self.device).synchronize()
@@ -652,11 +732,14 @@ class STTEngine:
                 self.stats["host_pre_s"] += t1 - t0
                 self.stats["gpu_wait_s"] += time.perf_counter() - t1
                 return out
-            max_q, host = self._host_meta(live, B_pad, T_pad, sot=sot)
+            max_q, host = self._host_meta(live, B_pad, T_pad, sot=sot, ts_ctl=ts_ctl)
             return self._host(self._fast_forward(self._dev(host), max_q, B_pad), B)
+        if self.timestamps:
+            return self._eager_step(live, sot, ts_ctl)
         return self._eager_step(live, sot) if self.sot_probe else self._eager_step(live)
 
-    def _eager_step(self, live: list[STTRequest], sot: list | None = None):
+    def _eager_step(self, live: list[STTRequest], sot: list | None = None,
+                    ts_ctl: list | None = None):
         """Reference decode path (hipBLASLt GEMMs, eager launches)."""
         T_enc = self.cfg.n_audio_ctx
         toks, pos, slots, cu, ctx, lidx = [], [], [], [0], [], []
@@ -683,12 +766,17 @@ class STTEngine:
             dev(toks, torch.int32), dev(pos, torch.int32), dev(slots, torch.int32),
             dev(cu, torch.int32), dev(ctx, torch.int32), dev(bt, torch.int32), max_q, max_ctx,
             self.kv.k, self.kv.v, self.xkv, enc_starts, enc_lens, dev(lidx, torch.int64), self.ws)
-        if not self.sot_probe:
+        if not self.row_fields:
             return self._host(self._argmax(logits))
         if sot is None:
             sot = [r.sot_pending for r in live]
         meta = {"mask_row": dev([1 if x else 0 for x in sot], torch.int32),
                 "probe": dev([self.nospeech if x else -1 for x in sot], torch.int32)}
+        if self.timestamps:
+            if ts_ctl is None:
+                ts_ctl = [self._ts_ctl(r) for r in live]
+            meta["ts_ctl"] = dev(list(ts_ctl), torch.int32)
+            meta["row_slot"] = dev([r.slot for r in live], torch.int32)
         return self._host(self._sample(logits, meta))
 
     # ----------------------------------------------------------- admission
@@ -749,6 +837,9 @@ class STTEngine:
             r.lp_sum, r.lp_n, r.avg_logprob = 0.0, 0, None
             r.language = r.language_prob = r.no_speech_prob = None
             r.no_speech_probs, r.lang_id, r.gated_windows = [], -1, 0
+            r.segments = r.open_segments = r.speech_start_s = r.speech_end_s = None
+            if self.timestamps:
+                r.segments, r.open_segments = [], []
             if not r.slots:
                 r.slots = [r.slot]
             self._begin_window(r, 0)
@@ -834,10 +925,14 @@ class STTEngine:
                 rest.append(r.feed[n:])
                 r.feed = r.feed[:n]
         live = step
-        nxt = self._step(live, [r.sot_pending and not x for r, x in zip(live, rest)]) \
-            if self.sot_probe else self._step(live)
+        if self.timestamps:
+            nxt = self._step(live, [r.sot_pending and not x for r, x in zip(live, rest)],
+                             [self._ts_ctl(r, bool(x)) for r, x in zip(live, rest)])
+        else:
+            nxt = self._step(live, [r.sot_pending and not x for r, x in zip(live, rest)]) \
+                if self.sot_probe else self._step(live)
         lps = plps = None
-        if self.sot_probe:
+        if self.row_fields:
             nxt, lps, plps = nxt
         elif self.token_logprobs:
             nxt, lps = nxt
@@ -868,6 +963,12 @@ class STTEngine:
         """Window ``r.win`` of ``r`` is decoded: start the next window (None)
         or complete the request (its windows' texts joined)."""
         toks = [x for x in r.tokens if x != self.eot]
+        segs = None
+        if self.timestamps and r.target is None:
+            # a freely decoded window: timestamp tokens cut it into segments;
+            # its text and the next window's prompt are the text tokens
+            segs = cut_window(r.tokens, self.ts_begin, self.eot)
+            toks = text_tokens(r.tokens, self.ts_begin, self.eot)
         self.kv.pool.free_seq(r.seq_id)
         # Whisper's no-speech rule, on a freely decoded window (a teacher-forced
         # one has no log-probabilities): its text is empty, its tokens stay out
@@ -881,6 +982,16 @@ class STTEngine:
             r.gated_windows += 1
             self.stats["no_speech_windows"] += 1
             r.win_texts.append("")
+        elif segs is not None:
+            out = utterance_segments(segs, r.win, r.n_samples / 16000.0,
+                                     lambda t: self.tok.decode(t, skip_from=self.ts_begin))
+            r.segments += out
+            r.win_texts.append(" ".join(t for _, _, t in out))
+            if segs and segs[-1].open:
+                r.open_segments.append(r.win)
+                self.stats["open_segments"] += 1
+            self.stats["timestamp_segments"] += len(out)
+            r.prev_tokens = (r.prev_tokens + toks)[-max(PREV_TOKENS, 1):]
         else:
             r.win_texts.append(self.tok.decode(toks).strip())
             r.prev_tokens = (r.prev_tokens + toks)[-max(PREV_TOKENS, 1):]
@@ -896,6 +1007,8 @@ class STTEngine:
         r.text = " ".join(t for t in r.win_texts if t)
         if r.no_speech_probs:
             r.no_speech_prob = min(r.no_speech_probs)
+        if r.segments:
+            r.speech_start_s, r.speech_end_s = r.segments[0][0], r.segments[-1][1]
         if r.gated_windows and r.gated_windows == r.windows:
             self.stats["no_speech_utterances"] += 1
         if r.lp_n:

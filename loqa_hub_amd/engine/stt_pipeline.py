@@ -143,10 +143,11 @@ class STTPipeline:
         C = min(eng.cfg.n_text_ctx, -(-ctx // eng.SPLIT_KEYS) * eng.SPLIT_KEYS)
         sot = [r.pl_launched == r.sot_step for r in rows] if eng.sot_probe else None
         if (B_pad, T_pad, C) not in eng._graphs and eng._graphs_frozen:
-            return self._launch_sync(rows, feeds, sot)
+            return self._launch_sync(rows, feeds, sot, self._ts_ctl(rows))
         g = eng._graph(B_pad, T_pad, C)
         hb = eng.io.stage(g)
-        eng._host_meta(rows, B_pad, T_pad, out=hb, feeds=feeds, sot=sot)
+        eng._host_meta(rows, B_pad, T_pad, out=hb, feeds=feeds, sot=sot,
+                       ts_ctl=self._ts_ctl(rows))
         stage_feeds(hb, feeds, [r.slot for r in rows], eng.io.trash)
         t_r = time.perf_counter()
         rslot = eng.io.replay(g)
@@ -165,7 +166,18 @@ class STTPipeline:
         eng.stats["decode_steps"] += 1
         return True
 
-    def _launch_sync(self, rows, feeds, sot=None) -> bool:
+    def _ts_ctl(self, rows):
+        """A timestamps engine's rule control words for the rows' next steps,
+        from the launch counts alone (the host has not seen the tokens of the
+        steps in flight): 0 = a prompt chunk before the last, the SOT probe step
+        and every step of a teacher-forced window, 1 = the step feeding the
+        window's last prompt token, 2 = later steps, whose state is on the device."""
+        if not self.eng.timestamps:
+            return None
+        return [0 if r.target is not None or r.pl_launched < r.prompt_steps - 1 else
+                1 if r.pl_launched == r.prompt_steps - 1 else 2 for r in rows]
+
+    def _launch_sync(self, rows, feeds, sot=None, ts_ctl=None) -> bool:
         """Bucket without a captured graph (serving never captures): finish
         what is in flight, then one synchronous step through ``STTEngine._step``."""
         if any(DEV in f for f in feeds):
@@ -173,7 +185,10 @@ class STTPipeline:
         saved = [r.feed for r in rows]
         for r, f in zip(rows, feeds):
             r.feed = f
-        res = self.eng._step(rows, sot) if sot is not None else self.eng._step(rows)
+        if ts_ctl is not None:
+            res = self.eng._step(rows, sot, ts_ctl)
+        else:
+            res = self.eng._step(rows, sot) if sot is not None else self.eng._step(rows)
         out = res[0] if self.eng.token_logprobs else res
         for r, f in zip(rows, saved):
             r.feed = f
@@ -199,7 +214,7 @@ class STTPipeline:
             st.event.synchronize()
         res = eng.io.result(st.out, st.B) if st.event is not None else st.out
         plps = None
-        if eng.sot_probe:
+        if eng.row_fields:
             nxt, lps, plps = res
         else:
             nxt, lps = res if eng.token_logprobs else (res, None)

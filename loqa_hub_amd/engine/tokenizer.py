@@ -151,11 +151,14 @@ class SyntheticTokenizer:
                 i += 1
         return ids
 
-    def decode(self, ids) -> str:
+    def decode(self, ids, skip_from: int | None = None) -> str:
+        """``skip_from``: ids at or above it are left out (timestamp tokens)."""
         out = []
         pending = bytearray()
         for t in ids:
             t = int(t)
+            if skip_from is not None and t >= skip_from:
+                continue
             if self.byte_base <= t < self.byte_base + 256:
                 pending.append(t - self.byte_base)
                 continue
@@ -212,6 +215,49 @@ class SyntheticWhisperTokenizer:
             if m:
                 out[m.group(1)] = i
         return out
+
+
+# Whisper's timestamp tokens <|0.00|> .. <|30.00|>, 0.02 s apart
+TS_COUNT = 1501
+TS_MIN = 11
+_TS_RE = re.compile(r"<\|(\d+\.\d\d)\|>")
+
+
+class SyntheticTimestampTokenizer:
+    """A synthetic Whisper tokenizer laid out as a checkpoint's for timestamp
+    decoding: the top ``ts_count`` ids of the vocabulary stand for the
+    timestamp tokens ``<|0.00|>`` .. (1501 when the reserved filler has room,
+    else as many as fit), and ``<|endoftext|>`` is the id just below them, so
+    every text id lies below it as Whisper's rules assume. A view of the base
+    tokenizer like ``SyntheticWhisperTokenizer`` (which it may wrap): the
+    claimed ids stay filler there, never encoded and without text."""
+
+    def __init__(self, base):
+        used = max([base.n_real] + [i + 1 for i in getattr(base, "_extra", {}).values()])
+        room = base.vocab_size - used - 1           # one id for <|endoftext|>
+        if room < TS_MIN:
+            raise ValueError("vocabulary too small for the Whisper timestamp tokens")
+        self._base = base
+        self.ts_count = min(TS_COUNT, room)
+        self.ts_begin = base.vocab_size - self.ts_count
+        self._eot = self.ts_begin - 1
+
+    def __getattr__(self, name):
+        return getattr(self._base, name)
+
+    def timestamp_tokens(self) -> tuple[int, int]:
+        return self.ts_begin, self.ts_count
+
+    def token_id(self, s: str) -> int:
+        if s == "<|endoftext|>":
+            return self._eot
+        m = _TS_RE.fullmatch(s)
+        if m:
+            k = round(float(m.group(1)) / 0.02)
+            if k >= self.ts_count or f"<|{k * 0.02:.2f}|>" != s:
+                raise KeyError(f"{s!r} is not a timestamp token of this tokenizer")
+            return self.ts_begin + k
+        return self._base.token_id(s)
 
 
 # ---------------------------------------------------------------------------
@@ -354,9 +400,33 @@ class HFTokenizer:
         ids = self._t.encode(text, add_special_tokens=False).ids
         return ([self.bos] if bos and self.bos is not None else []) + ids
 
-    def decode(self, ids) -> str:
-        return self._t.decode([int(t) for t in ids if 0 <= int(t) < self.n_real],
+    def decode(self, ids, skip_from: int | None = None) -> str:
+        """``skip_from``: ids at or above it are left out (timestamp tokens)."""
+        top = self.n_real if skip_from is None else min(self.n_real, int(skip_from))
+        return self._t.decode([int(t) for t in ids if 0 <= int(t) < top],
                               skip_special_tokens=True)
+
+    def timestamp_tokens(self) -> tuple[int, int]:
+        """(ts_begin, ts_count): the run of ``<|d.dd|>`` added tokens that starts
+        at ``<|0.00|>``, 0.02 s apart, with consecutive ids, the last tokens of
+        the file (Whisper's layout; the decoder's rules rely on it)."""
+        ts = {}
+        for i, t in self._added.items():
+            m = _TS_RE.fullmatch(str(getattr(t, "content", t)))
+            if m:
+                ts[i] = m.group(1)
+        begin = self._t.token_to_id("<|0.00|>")
+        if begin is None or not ts:
+            raise ValueError("the tokenizer has no <|0.00|> timestamp token")
+        count = 0
+        while ts.get(begin + count) == f"{count * 0.02:.2f}":
+            count += 1
+        if count != len(ts) or min(ts) != begin:
+            raise ValueError("the tokenizer's timestamp tokens are not one contiguous run of "
+                             "0.02 s steps from <|0.00|>")
+        if begin + count != self.n_real:
+            raise ValueError("the tokenizer's timestamp tokens are not its last tokens")
+        return begin, count
 
     def token_text(self, t: int) -> str:
         return self._text[t] if 0 <= t < self.n_real else ""

@@ -34,6 +34,11 @@ class TranscriptionResult:
     language: str | None = None
     language_prob: float | None = None
     no_speech_prob: float | None = None
+    # HUB_STT_TIMESTAMPS=segment (gpu backend; else None): (start_s, end_s, text)
+    # segments in utterance time, the first one's start and the last one's end
+    segments: list | None = None
+    speech_start_s: float | None = None
+    speech_end_s: float | None = None
 
 
 @dataclass
@@ -99,16 +104,21 @@ def post_process_transcription(raw: str) -> PostProcessingResult:
 def to_transcription_result(raw: str, avg_logprob: float | None = None,
                             confirm_below: float = CONFIRMATION_THRESHOLD, *,
                             language: str | None = None, language_prob: float | None = None,
-                            no_speech_prob: float | None = None) -> TranscriptionResult:
+                            no_speech_prob: float | None = None, segments: list | None = None,
+                            speech_start_s: float | None = None,
+                            speech_end_s: float | None = None) -> TranscriptionResult:
     """``avg_logprob`` (the on-device Whisper decode's mean token
     log-probability): the confidence is the geometric-mean token probability
     ``min(1, exp(avg_logprob))`` instead of the text heuristic, and a
     confirmation is needed below ``confirm_below``. None: the reference's
     heuristic and threshold. The wake-word-only rule holds either way.
     ``language`` / ``language_prob`` / ``no_speech_prob``: what the decoder read
-    at the start-of-transcript position, carried as they are."""
+    at the start-of-transcript position, carried as they are; so are
+    ``segments`` / ``speech_start_s`` / ``speech_end_s`` of a decode with
+    timestamps (their texts are the decoder's, before the wake-word cut)."""
     p = post_process_transcription(raw)
-    probe = dict(language=language, language_prob=language_prob, no_speech_prob=no_speech_prob)
+    probe = dict(language=language, language_prob=language_prob, no_speech_prob=no_speech_prob,
+                 segments=segments, speech_start_s=speech_start_s, speech_end_s=speech_end_s)
     if avg_logprob is None:
         return TranscriptionResult(p.cleaned_text, p.confidence_estimate, p.wake_word_detected,
                                    p.wake_word_variant, p.needs_confirmation, **probe)

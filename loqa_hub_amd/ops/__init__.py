@@ -361,6 +361,50 @@ def masked_argmax_logprob_probe(logits: torch.Tensor, mask: torch.Tensor | None,
     return out, lp, plp
 
 
+def masked_argmax_timestamps(logits: torch.Tensor, mask: torch.Tensor | None,
+                             mask_rows: torch.Tensor | None, probe: torch.Tensor,
+                             ts_ctl: torch.Tensor, ts_state: torch.Tensor, row_slot: torch.Tensor,
+                             ts_begin: int, ts_count: int, eot: int, max_initial: int
+                             ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``masked_argmax_logprob_probe`` under Whisper's timestamp rules, decided
+    on the device (``ops.reference.masked_argmax_timestamps`` has the rules).
+    ``ts_ctl`` int32 [B]: 0 = rules off, the row is
+    ``masked_argmax_logprob_probe``'s bit for bit; 1 = the window's first
+    sampled token; 2 = continue from ``ts_state[row_slot[b]]``. ``ts_state``
+    int32 [slots] is read and updated in place by the ruled rows (their slots
+    must differ). Timestamp token k is column ``ts_begin + k``, k < ``ts_count``;
+    columns below ``eot`` are text; ``max_initial`` (clamped to ``ts_count -
+    1``) bounds a window's first timestamp. Returns (int32 [B], float32 [B],
+    float32 [B])."""
+    assert logits.dim() == 2 and logits.stride(-1) == 1
+    B, V = logits.shape
+    for t in (probe, ts_ctl, row_slot):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == B
+        assert t.device == logits.device
+    assert ts_state.dtype == torch.int32 and ts_state.is_contiguous() and ts_state.dim() == 1
+    assert ts_state.device == logits.device
+    if not (0 <= eot <= ts_begin and ts_count >= 1 and ts_begin + ts_count <= V
+            and max_initial >= 0):
+        raise ValueError(f"timestamp layout eot={eot} ts_begin={ts_begin} ts_count={ts_count} "
+                         f"max_initial={max_initial} does not fit {V} logits")
+    max_initial = min(int(max_initial), ts_count - 1)
+    if probe.device.type == "cpu" and B:
+        if int(probe.max()) >= V:
+            raise ValueError(f"probe column {int(probe.max())} is outside the {V} logits")
+        ruled = row_slot[(ts_ctl == 1) | (ts_ctl == 2)]
+        assert ruled.numel() == ruled.unique().numel(), "two ruled rows share a state slot"
+        assert not ruled.numel() or (0 <= int(ruled.min()) and int(ruled.max()) < ts_state.numel())
+    if not _gpu(logits):
+        return ref.masked_argmax_timestamps(logits, mask, mask_rows, probe, ts_ctl, ts_state,
+                                            row_slot, ts_begin, ts_count, eot, max_initial)
+    head, out, (lp, plp), ws = _argmax_args(logits, mask, mask_rows, 2, 6)   # 48-byte records
+    check(kernels().loqa_masked_argmax_ts(
+        *head, ptr(probe), ptr(ts_ctl), ptr(ts_state), ptr(row_slot), ts_state.numel(), ts_begin,
+        ts_count, eot, max_initial, ptr(out), ptr(lp), ptr(plp), ptr(ws), stream_ptr(logits)),
+        "masked_argmax_ts")
+    return out, lp, plp
+
+
 # -------------------------------------------------------------------- audio
 def pcm16_to_f32_sumsq(pcm: torch.Tensor, offsets: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     """pcm: int16 [N] (concatenated segments), offsets: int64 [S+1].

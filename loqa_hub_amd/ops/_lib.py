@@ -168,6 +168,11 @@ _KERNEL_SIGS = {
     # (out, lp, lp2, n, res, stride, res_lp, lp_stride, plane, nres, ctr, row_slot, last_tok, stream)
     "loqa_step_publish_lp2": [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
                               c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "loqa_masked_argmax_ts": [c_void_p, c_int, c_ll, c_int, c_int, c_void_p, c_void_p, c_int,
+                              # (..., probe, ts_ctl, ts_state, row_slot, slots, ts_begin, ts_count,
+                              #  eot, max_initial, out_idx, out_logprob, out_probe, workspace, stream)
+                              c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                              c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
 }
 
 # (argtypes, restype) of the custom all-reduce entry points (in the kernels library)

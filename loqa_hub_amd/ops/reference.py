@@ -196,6 +196,100 @@ def masked_argmax_logprob_probe(logits, mask, mask_rows, probe, token_ids=None):
     return idx, lp, plp
 
 
+def ts_state_pack(last: int, f_last: bool, f_pen: bool) -> int:
+    """The timestamp-rule state word of one decoder sequence: ``last`` = the
+    last timestamp index sampled in the window (-1: none), ``f_last`` = the last
+    sampled token was a timestamp, ``f_pen`` = the one before it was (or fewer
+    than two tokens have been sampled)."""
+    return ((int(last) + 1) << 2) | (int(bool(f_last)) << 1) | int(bool(f_pen))
+
+
+def ts_state_unpack(word: int) -> tuple[int, bool, bool]:
+    """``ts_state_pack`` reversed: (last, f_last, f_pen)."""
+    word = int(word)
+    return (word >> 2) - 1, bool((word >> 1) & 1), bool(word & 1)
+
+
+def ts_state_next(word: int, ctl: int, winner: int, ts_begin: int) -> int:
+    """The state word after a ruled row (``ctl`` 1 or 2) sampled ``winner``."""
+    last, f_last, _ = (-1, False, True) if ctl == 1 else ts_state_unpack(word)
+    is_ts = winner >= ts_begin
+    return ts_state_pack(winner - ts_begin if is_ts else last, is_ts, True if ctl == 1 else f_last)
+
+
+def ts_allowed(word: int, ctl: int, ts_count: int, max_initial: int) -> tuple[int, int, int]:
+    """Whisper's timestamp rules for a ruled row as ``(text_ok, lo, hi)``:
+    ``text_ok`` 2 = every column below ``ts_begin`` that the mask allows, 1 =
+    only those at or above ``eot`` (a lone timestamp is followed by a timestamp
+    or EOT), 0 = none (a window opens with a timestamp); ``lo .. hi`` = the
+    timestamp indices allowed (``lo > hi``: none, the token after a closed pair
+    is text). ``ctl`` 1 ignores ``word``."""
+    if ctl == 1:
+        return 0, 0, min(int(max_initial), ts_count - 1)
+    last, f_last, f_pen = ts_state_unpack(word)
+    hi = ts_count - 1
+    if f_last and f_pen:
+        return 2, hi + 1, hi
+    lo = 0 if last < 0 else (last if f_last and not f_pen else last + 1)
+    return (1 if f_last and not f_pen else 2), min(lo, hi + 1), hi
+
+
+def ts_mass_rule(lse_t, lse_a, xt):
+    """The f32 comparison of Whisper's mass rule, as the kernel spells it: the
+    timestamps' log-probability mass against the best text token's."""
+    return (lse_t - lse_a) > (xt - lse_a)
+
+
+def masked_argmax_timestamps(logits, mask, mask_rows, probe, ts_ctl, ts_state, row_slot,
+                             ts_begin, ts_count, eot, max_initial):
+    """``masked_argmax_logprob_probe`` under Whisper's timestamp rules
+    (``ApplyTimestampRules`` as a state machine, see ``ts_allowed``), in fp32.
+    A row with ``ts_ctl[b] == 0`` is ``masked_argmax_logprob_probe``'s. A ruled
+    row selects among A = the mask's columns below ``ts_begin`` that the rules
+    leave plus the timestamp columns ``ts_begin + lo .. ts_begin + hi`` (their
+    mask bits ignored): the best timestamp, with its log-softmax over the
+    allowed timestamps, when logsumexp(timestamps) - logsumexp(A) exceeds the
+    best other logit - logsumexp(A) (or nothing else is allowed), else the best
+    other column with its log-softmax over A. It then updates
+    ``ts_state[row_slot[b]]`` in place; nothing allowed: (-1, -inf), the state
+    unchanged. Returns (int32 [B], float32 [B], float32 [B])."""
+    idx, lp, plp = masked_argmax_logprob_probe(logits, mask, mask_rows, probe)
+    x = logits.float()
+    B, V = x.shape
+    ninf = float("-inf")
+    max_initial = min(int(max_initial), ts_count - 1)
+    for b in range(B):
+        ctl = int(ts_ctl[b])
+        if ctl not in (1, 2):
+            continue
+        slot = int(row_slot[b])
+        word = int(ts_state[slot])
+        text_ok, lo, hi = ts_allowed(word, ctl, ts_count, max_initial)
+        if mask is not None:
+            okx = unpack_mask(mask[int(mask_rows[b]) if mask_rows is not None else b], V).clone()
+        else:
+            okx = torch.ones(V, dtype=torch.bool)
+        okx[ts_begin:] = False
+        okx[: (ts_begin, eot, 0)[text_ok]] = False
+        okt = torch.zeros(V, dtype=torch.bool)
+        okt[ts_begin + lo: ts_begin + hi + 1] = True
+        xx = x[b].masked_fill(~okx, ninf)
+        xt_ = x[b].masked_fill(~okt, ninf)
+        any_x, any_t = bool(okx.any()), bool(okt.any())
+        lse_a = torch.logsumexp(x[b].masked_fill(~(okx | okt), ninf), dim=-1)
+        lse_t = torch.logsumexp(xt_, dim=-1)
+        fire = any_t and (not any_x or bool(ts_mass_rule(lse_t, lse_a, xx.max())))
+        if not (any_x or any_t):
+            idx[b], lp[b] = -1, ninf
+            continue
+        row, lse = (xt_, lse_t) if fire else (xx, lse_a)
+        w = int(row.argmax())
+        idx[b] = w
+        lp[b] = row[w] - lse if row[w] != ninf else ninf
+        ts_state[slot] = ts_state_next(word, ctl, w, ts_begin)
+    return idx, lp, plp
+
+
 def unpack_mask(m: torch.Tensor, V: int) -> torch.Tensor:
     """int32 words [..., W] -> bool [..., V]"""
     shifts = torch.arange(32, device=m.device, dtype=torch.int32)

@@ -49,6 +49,12 @@ LABELS.update({
         f"{'V <= 8192' if single else 'chunked'}"
     for mode in (0, 1, 2) for bf in (True, False) for single in (True, False)})
 LABELS.update({f"argmax_finalize_kernel<{mode}>": f"argmax finalize, mode {mode}" for mode in (0, 1, 2)})
+# MODE 3 (Whisper's timestamp rules) takes its arguments as a trailing TsArgs
+LABELS.update({
+    f"masked_argmax_kernel<{str(bf).lower()}, {str(single).lower()}, 3, TsArgs>":
+        f"argmax + timestamp rules, {'bf16' if bf else 'f32'}, {'V <= 8192' if single else 'chunked'}"
+    for bf in (True, False) for single in (True, False)})
+LABELS["argmax_finalize_kernel<3, TsArgs>"] = "argmax finalize, mode 3"
 PAT = {"V": r"VGPRs: (\d+)", "A": r"AGPRs: (\d+)", "occ": r"Occupancy \[waves/SIMD\]: (\d+)",
        "LDS": r"LDS Size \[bytes/block\]: (\d+)", "spill": r"VGPRs Spill: (\d+)"}
 
