@@ -324,8 +324,8 @@ extern "C" int loqa_pcm16_f32_pad(const void* pcm, float* out, const long long* 
 }
 
 // --------------------------------------------------- K15 grammar-masked argmax
-// One row scan in four modes behind loqa_masked_argmax (MODE 0), _lse (1),
-// _lse_probe (2) and _ts (3). The modes share the arithmetic and its order, so a higher
+// One row scan in five modes behind loqa_masked_argmax (MODE 0), _lse (1),
+// _lse_probe (2), _ts (3) and _sample (4). The modes share the arithmetic and its order, so a higher
 // mode returns the lower modes' results bit for bit.
 // logits: [B, V] (bf16 if is_bf16 else f32), row stride ld elements.
 // mask: [*, W] uint32 bitmask (bit v%32 of word v/32 = token v allowed), or null;
@@ -355,8 +355,8 @@ extern "C" int loqa_pcm16_f32_pad(const void* pcm, float* out, const long long* 
 // with probe[b] < 0 or >= V writes +0.0f and skips the second sum; the test is
 // per row (blockIdx.y), so wave-uniform.
 // A row is split over ARG_CHUNK-token workgroups (a 128k vocabulary -> 16 per
-// row, so B=16 rows fill the GPU). Each reduces its tokens to one record (8, 16
-// or 32 bytes by mode) in a fixed order: vector groups in column order, the
+// row, so B=16 rows fill the GPU). Each reduces its tokens to one record (8, 16,
+// 32, 48 or 64 bytes by mode) in a fixed order: vector groups in column order, the
 // shuffle tree 32 -> 1, the waves in wave order. A row of one chunk finishes
 // there (SINGLE): one launch, no workspace. A wider row in MODE 0 folds its
 // records with atomicMax into a zeroed word per row, which a small launch
@@ -456,6 +456,10 @@ template <> struct ArgRec<3> : ArgRec<2> {
   unsigned long long tbest;   // the best allowed timestamp column
   float tm, tsum;             // allowed timestamp columns (ruled rows)
 };
+template <> struct ArgRec<4> : ArgRec<3> {
+  unsigned long long gbest;   // sampling rows: the best Gumbel key below ts_begin
+  unsigned long long gtbest;  // ... and among the allowed timestamp columns
+};
 
 // MODE 3: Whisper's timestamp rules as a state machine beside the scan. ctl[b]:
 // 0 = rules off (the row is MODE 2's, the state untouched), 1 = the window's
@@ -507,6 +511,71 @@ __device__ __forceinline__ TsRow ts_row(const TsArgs& t, int b, int V) {
   return r;
 }
 
+// MODE 4: MODE 3 plus a per-row temperature temp[b] and a random key rng[b]. A
+// row with temp[b] == 0 (or not > 0) is MODE 3's bit for bit. A row with
+// temp[b] > 0 draws its token by Gumbel-max in the same pass: every column the
+// row may select keeps key = fmaf(T, g, x), g = gumbel_noise(rng[b], column),
+// and the largest key per class (gbest / gtbest, ties to the lowest column)
+// rides along in the record. The greedy quantities are accumulated as in MODE
+// 3 and the mass rule is evaluated on them, at temperature 1, before the draw:
+// it fires -> the winner is gtbest, else max(gbest, gtbest), a draw from
+// Categorical(logits / T) over what the rules leave. The finishing thread loads
+// x[winner] and writes its log-probability at temperature 1 (Whisper's
+// sum_logprobs), over the timestamps when the rule fired, else over every
+// allowed column. ctl == nullptr: every row rule-off, the layout ignored.
+struct SampleArgs : TsArgs {
+  const float* temp;
+  const uint32_t* rng;
+  const void* logits;   // the finishing thread's load of x[winner]
+  long long ld;
+  int is_bf16;
+};
+
+__device__ __forceinline__ TsRow ts_row(const SampleArgs& t, int b, int V) {
+  if (t.ctl) return ts_row(static_cast<const TsArgs&>(t), b, V);
+  TsRow r;
+  r.ctl = r.slot = r.f_last = 0, r.last = -1;
+  r.x_from = 0, r.x_to = V, r.t_from = r.t_to = 0;
+  return r;
+}
+__device__ __forceinline__ float sample_temp(const SampleArgs& t, int b) { return t.temp[b]; }
+__device__ __forceinline__ uint32_t sample_rng(const SampleArgs& t, int b) { return t.rng[b]; }
+__device__ __forceinline__ float sample_x(const SampleArgs& t, int b, int col) {
+  const size_t i = (size_t)b * t.ld + col;
+  return t.is_bf16 ? bf2f(reinterpret_cast<const bf16_t*>(t.logits)[i])
+                   : reinterpret_cast<const float*>(t.logits)[i];
+}
+
+__device__ __forceinline__ uint32_t fmix32(uint32_t h) {
+  h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
+  return h;
+}
+
+// Counter-based standard Gumbel noise of (row key, column): h = fmix32(rng ^
+// fmix32(v + 0x9E3779B9)), u = (2 (h >> 9) + 1) / 2^24, an exact f32 strictly
+// inside (0, 1), so g = -log(-log u) is finite (about -2.9 .. 16.7). The
+// integer part is ops.reference.gumbel_uniform; the two logf and the key's fmaf
+// are spelled out with contraction off so the bits do not depend on the call
+// site (loqa_gumbel_noise writes g through this function).
+__device__ __forceinline__ float gumbel_noise(uint32_t rng, int v) {
+#pragma clang fp contract(off)
+  const uint32_t h = fmix32(rng ^ fmix32((uint32_t)v + 0x9E3779B9u));
+  const float u = (float)(2u * (h >> 9) + 1u) * (1.0f / 16777216.0f);
+  const float w = 0.f - logf(u);
+  return 0.f - logf(w);
+}
+__device__ __forceinline__ void gumbel_one(unsigned long long& best, float x, int v, float T,
+                                           uint32_t rng) {
+  best = max(best, argpack(fmaf(T, gumbel_noise(rng, v), x), v));
+}
+template <int N>
+__device__ __forceinline__ void gumbel_group(unsigned long long& best, const float (&f)[N],
+                                             uint32_t bits, int v0, float T, uint32_t rng) {
+#pragma unroll
+  for (int j = 0; j < N; ++j)
+    if ((bits >> j) & 1u) gumbel_one(best, f[j], v0 + j, T, rng);
+}
+
 // bit j: column v0 + j lies in [from, to); N <= 8 columns
 __device__ __forceinline__ uint32_t range_bits(int v0, int N, int from, int to) {
   const int a = min(max(from - v0, 0), N), e = min(max(to - v0, 0), N);
@@ -533,7 +602,8 @@ struct ArgAcc : ArgRec<MODE> {
     this->best = 0;
     if constexpr (MODE >= 1) this->m = -INFINITY, this->s = 0.f;
     if constexpr (MODE >= 2) this->am = this->px = -INFINITY, this->as = this->pad = 0.f;
-    if constexpr (MODE == 3) this->tbest = 0, this->tm = -INFINITY, this->tsum = 0.f;
+    if constexpr (MODE >= 3) this->tbest = 0, this->tm = -INFINITY, this->tsum = 0.f;
+    if constexpr (MODE == 4) this->gbest = this->gtbest = 0;
   }
   __device__ __forceinline__ ArgAcc(const ArgRec<MODE>& r) : ArgRec<MODE>(r) {}
 
@@ -583,22 +653,29 @@ struct ArgAcc : ArgRec<MODE> {
   // the field itself, or in the shuffle tree the same field of another lane, so
   // that a probing row's extra shuffles and sums stay one block. `ruled` (MODE
   // 3, per row): the timestamp class is merged too, in the masked pair's form.
+  // `sampling` (MODE 4, per row): the two Gumbel bests too.
   template <bool FMA, class Get>
-  __device__ __forceinline__ void merge(const ArgRec<MODE>& o, bool probing, bool ruled, Get get) {
+  __device__ __forceinline__ void merge(const ArgRec<MODE>& o, bool probing, bool ruled,
+                                        bool sampling, Get get) {
     this->best = max(this->best, get(o.best));
     if constexpr (MODE >= 1) lse_merge<FMA>(this->m, this->s, get(o.m), get(o.s));
     if constexpr (MODE >= 2) if (probing) {
       lse_merge<false>(this->am, this->as, get(o.am), get(o.as));   // <false> at every site
       this->px = fmaxf(this->px, get(o.px));
     }
-    if constexpr (MODE == 3) if (ruled) {
+    if constexpr (MODE >= 3) if (ruled) {
       this->tbest = max(this->tbest, get(o.tbest));
       lse_merge<FMA>(this->tm, this->tsum, get(o.tm), get(o.tsum));
     }
+    if constexpr (MODE == 4) if (sampling) {
+      this->gbest = max(this->gbest, get(o.gbest));
+      if (ruled) this->gtbest = max(this->gtbest, get(o.gtbest));
+    }
   }
   template <bool FMA>
-  __device__ __forceinline__ void merge(const ArgRec<MODE>& o, bool probing, bool ruled) {
-    merge<FMA>(o, probing, ruled, [](auto x) { return x; });
+  __device__ __forceinline__ void merge(const ArgRec<MODE>& o, bool probing, bool ruled,
+                                        bool sampling) {
+    merge<FMA>(o, probing, ruled, sampling, [](auto x) { return x; });
   }
 
   __device__ __forceinline__ void finish(int b, bool probing, const int* __restrict__ token_ids,
@@ -640,6 +717,38 @@ struct ArgAcc : ArgRec<MODE> {
     const int last = f_last ? col - t.ts_begin : r.last;
     t.state[r.slot] = ((last + 1) << 2) | (f_last << 1) | (r.ctl == 1 ? 1 : r.f_last);
   }
+
+  // MODE 4: a row with temp[b] == 0 finishes as MODE 3 does. A sampling row's
+  // winner is a Gumbel best (see SampleArgs); its log-probability is taken at
+  // temperature 1 from the greedy sums, x[winner] loaded here.
+  __device__ __forceinline__ void finish(int b, bool probing, const TsRow& r, const SampleArgs& t,
+                                         int* __restrict__ out_idx, float* __restrict__ out_logprob,
+                                         float* __restrict__ out_probe) const {
+    if (!(sample_temp(t, b) > 0.f)) {
+      finish(b, probing, r, static_cast<const TsArgs&>(t), out_idx, out_logprob, out_probe);
+      return;
+    }
+    out_probe[b] = lse_probe_logprob(probing, this->px, this->am, this->as);
+    float mA = this->m, sA = this->s;
+    bool fire = false;
+    if (r.ctl != 0) {
+      lse_merge<false>(mA, sA, this->tm, this->tsum);
+      fire = ts_fires(this->best != 0, this->tbest != 0, this->m, mA, sA, this->tm, this->tsum);
+    }
+    const int col = argunpack(fire ? this->gtbest : max(this->gbest, this->gtbest), nullptr);
+    out_idx[b] = col;
+    if (col < 0) {                     // nothing allowed: the state stays
+      out_logprob[b] = -INFINITY;
+      return;
+    }
+    const float xw = sample_x(t, b, col);
+    const float lm = fire ? this->tm : mA, ls = fire ? this->tsum : sA;
+    out_logprob[b] = xw != -INFINITY ? (xw - lm) - logf(ls) : -INFINITY;
+    if (r.ctl == 0) return;
+    const int f_last = col >= t.ts_begin;
+    const int last = f_last ? col - t.ts_begin : r.last;
+    t.state[r.slot] = ((last + 1) << 2) | (f_last << 1) | (r.ctl == 1 ? 1 : r.f_last);
+  }
 };
 
 __device__ __forceinline__ float arg_load(const bf16_t* p) { return bf2f(*p); }
@@ -655,14 +764,15 @@ __device__ __forceinline__ void arg_load_group(const float* p, float (&f)[4]) {
 // SINGLE: gridDim.x == 1 (V <= ARG_CHUNK); the workgroup writes the row's
 // results. Otherwise `part` is the zeroed packed word per row (MODE 0) or the
 // [B, gridDim.x] chunk records.
-// TS: empty below MODE 3 (the kernel's arguments are the lower modes' own), else TsArgs.
+// TS: empty below MODE 3 (the kernel's arguments are the lower modes' own), else TsArgs
+// (MODE 4: SampleArgs).
 template <bool BF16, bool SINGLE, int MODE, class... TS>
 __global__ __launch_bounds__(ARG_THREADS) void masked_argmax_kernel(
     const void* __restrict__ logits, long long ld, int V, const uint32_t* __restrict__ mask,
     const int* __restrict__ mask_rows, int W, const int* __restrict__ probe,
     ArgRec<MODE>* __restrict__ part, const int* __restrict__ token_ids, int* __restrict__ out_idx,
     float* __restrict__ out_logprob, float* __restrict__ out_probe, TS... ts) {
-  static_assert(sizeof...(TS) == (MODE == 3 ? 1 : 0), "MODE 3 takes one TsArgs");
+  static_assert(sizeof...(TS) == (MODE >= 3 ? 1 : 0), "MODE 3 / 4 take one TsArgs / SampleArgs");
   using T = typename std::conditional<BF16, bf16_t, float>::type;
   constexpr int N = BF16 ? 8 : 4;           // one 16-byte load
   __shared__ ArgRec<MODE> sred[ARG_THREADS / 64];
@@ -675,9 +785,13 @@ __global__ __launch_bounds__(ARG_THREADS) void masked_argmax_kernel(
   if constexpr (MODE >= 2) pb = probe[b];
   const bool probing = pb >= 0 && pb < V;   // false below MODE 2
   TsRow tr;
-  if constexpr (MODE == 3) tr = ts_row(ts..., b, V);
+  if constexpr (MODE >= 3) tr = ts_row(ts..., b, V);
   bool ruled = false;                       // per row too; false below MODE 3
-  if constexpr (MODE == 3) ruled = tr.ctl != 0;
+  if constexpr (MODE >= 3) ruled = tr.ctl != 0;
+  float temp = 0.f;                         // per row too; MODE 4 alone samples
+  uint32_t rng = 0;
+  if constexpr (MODE == 4) temp = sample_temp(ts..., b), rng = sample_rng(ts..., b);
+  const bool sampling = temp > 0.f;
   const T* row = reinterpret_cast<const T*>(logits) + (size_t)b * ld;
   ArgAcc<MODE> a;
   for (int v0 = v_begin + threadIdx.x * N; v0 < v_end; v0 += ARG_THREADS * N) {
@@ -686,37 +800,47 @@ __global__ __launch_bounds__(ARG_THREADS) void masked_argmax_kernel(
       arg_load_group(row + v0, f);
       const uint32_t all = (1u << N) - 1u;
       uint32_t bits = m ? (m[v0 >> 5] >> (v0 & 31)) & all : all;
-      if constexpr (MODE == 3) if (ruled) bits &= range_bits(v0, N, tr.x_from, tr.x_to);
+      if constexpr (MODE >= 3) if (ruled) bits &= range_bits(v0, N, tr.x_from, tr.x_to);
       a.template group<N>(f, bits, v0, probing, pb);
-      if constexpr (MODE == 3) if (ruled) {
+      if constexpr (MODE == 4) if (sampling) gumbel_group<N>(a.gbest, f, bits, v0, temp, rng);
+      if constexpr (MODE >= 3) if (ruled) {
         const uint32_t tbits = range_bits(v0, N, tr.t_from, tr.t_to);
-        if (tbits) a.template tgroup<N>(f, tbits, v0);
+        if (tbits) {
+          a.template tgroup<N>(f, tbits, v0);
+          if constexpr (MODE == 4) if (sampling) gumbel_group<N>(a.gtbest, f, tbits, v0, temp, rng);
+        }
       }
     } else {
       for (int v = v0; v < min(v_end, v0 + N); ++v) {
         bool ok = !m || ((m[v >> 5] >> (v & 31)) & 1u);
         bool tok = false;
-        if constexpr (MODE == 3) if (ruled) {
+        if constexpr (MODE >= 3) if (ruled) {
           ok = ok && v >= tr.x_from && v < tr.x_to;
           tok = v >= tr.t_from && v < tr.t_to;
         }
         if (ok || probing || tok) {
           const float x = arg_load(row + v);
           a.one(x, v, ok, probing, pb);
-          if constexpr (MODE == 3) if (tok) a.tone(x, v);
+          if constexpr (MODE >= 3) if (tok) a.tone(x, v);
+          if constexpr (MODE == 4) if (sampling) {
+            if (ok) gumbel_one(a.gbest, x, v, temp, rng);
+            if (tok) gumbel_one(a.gtbest, x, v, temp, rng);
+          }
         }
       }
     }
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1)   // shuffle tree: <true>, the masked pair's 2nd product fused
-    a.template merge<true>(a, probing, ruled, [o](auto x) { return __shfl_xor(x, o, 64); });
+    a.template merge<true>(a, probing, ruled, sampling,
+                           [o](auto x) { return __shfl_xor(x, o, 64); });
   if ((threadIdx.x & 63) == 0) sred[threadIdx.x >> 6] = a;
   __syncthreads();
   if (threadIdx.x == 0) {
     // LDS fold: <true>, as the shuffle tree
-    for (int i = 1; i < ARG_THREADS / 64; ++i) a.template merge<true>(sred[i], probing, ruled);
-    if constexpr (SINGLE && MODE == 3)   // every thread read the old state before the barrier
+    for (int i = 1; i < ARG_THREADS / 64; ++i)
+      a.template merge<true>(sred[i], probing, ruled, sampling);
+    if constexpr (SINGLE && MODE >= 3)   // every thread read the old state before the barrier
       a.finish(b, probing, tr, ts..., out_idx, out_logprob, out_probe);
     else if (SINGLE)
       a.finish(b, probing, token_ids, out_idx, out_logprob, out_probe);
@@ -740,24 +864,27 @@ __global__ void argmax_finalize_kernel(
   if constexpr (MODE >= 2) pb = probe[b];
   const bool probing = pb >= 0 && pb < V;
   TsRow tr;
-  if constexpr (MODE == 3) tr = ts_row(ts..., b, V);
+  if constexpr (MODE >= 3) tr = ts_row(ts..., b, V);
   bool ruled = false;
-  if constexpr (MODE == 3) ruled = tr.ctl != 0;
+  if constexpr (MODE >= 3) ruled = tr.ctl != 0;
+  bool sampling = false;
+  if constexpr (MODE == 4) sampling = sample_temp(ts..., b) > 0.f;
   const ArgRec<MODE>* p = part + (size_t)b * chunks;
   ArgAcc<MODE> a(p[0]);
-  for (int c = 1; c < chunks; ++c) a.template merge<false>(p[c], probing, ruled);   // chunks: <false>
-  // MODE 3: the scan launch has finished, so no workgroup still reads the old state
-  if constexpr (MODE == 3)
+  for (int c = 1; c < chunks; ++c)   // chunks: <false>
+    a.template merge<false>(p[c], probing, ruled, sampling);
+  // MODE >= 3: the scan launch has finished, so no workgroup still reads the old state
+  if constexpr (MODE >= 3)
     a.finish(b, probing, tr, ts..., out_idx, out_logprob, out_probe);
   else
     a.finish(b, probing, token_ids, out_idx, out_logprob, out_probe);
 }
 
-// The argument checks and the SINGLE / chunked dispatch of the three entry
+// The argument checks and the SINGLE / chunked dispatch of the five entry
 // points; probe, out_logprob and out_probe are null below their mode.
 // workspace (device, 8-byte aligned, only touched when V > ARG_CHUNK):
 // MODE 0: >= B * 8 bytes, zeroed here; MODE 1 / 2: >= B * ceil(V / ARG_CHUNK)
-// * 16 / 32 bytes (MODE 3: 48), no initialisation needed.
+// * 16 / 32 bytes (MODE 3: 48, MODE 4: 64), no initialisation needed.
 template <int MODE, class... TS>
 static int masked_argmax(const void* logits, int is_bf16, long long ld, int B, int V,
                          const uint32_t* mask, const int* mask_rows, int W, const int* probe,
@@ -829,6 +956,50 @@ extern "C" int loqa_masked_argmax_ts(const void* logits, int is_bf16, long long 
                  min(max_initial, ts_count - 1)};
   return masked_argmax<3>(logits, is_bf16, ld, B, V, mask, mask_rows, W, probe, out_idx,
                           out_logprob, out_probe, workspace, nullptr, s, t);
+}
+
+// MODE 4 (see SampleArgs): loqa_masked_argmax_ts plus temp: f32 [B] and rng:
+// uint32 [B]. ts_ctl == nullptr: every row rule-off (ts_state, row_slot and the
+// layout arguments are ignored), so an engine without timestamps can sample.
+// workspace: 64 bytes per (row, chunk).
+extern "C" int loqa_masked_argmax_sample(const void* logits, int is_bf16, long long ld, int B,
+                                         int V, const uint32_t* mask, const int* mask_rows, int W,
+                                         const int* probe, const int* ts_ctl, int* ts_state,
+                                         const int* row_slot, int slots, int ts_begin,
+                                         int ts_count, int eot, int max_initial, const float* temp,
+                                         const unsigned* rng, int* out_idx, float* out_logprob,
+                                         float* out_probe, void* workspace, hipStream_t s) {
+  if (B > 0 && (!temp || !rng)) return (int)hipErrorInvalidValue;
+  if (B > 0 && ts_ctl &&
+      (!ts_state || !row_slot || slots <= 0 || ts_count <= 0 || eot < 0 || eot > ts_begin ||
+       ts_begin > V - ts_count || max_initial < 0))
+    return (int)hipErrorInvalidValue;
+  SampleArgs t;
+  if (ts_ctl) {
+    static_cast<TsArgs&>(t) = TsArgs{ts_ctl, ts_state, row_slot, slots, ts_begin, ts_count, eot,
+                                     min(max_initial, ts_count - 1)};
+  } else {
+    static_cast<TsArgs&>(t) = TsArgs{nullptr, nullptr, nullptr, 0, V, 0, V, 0};
+  }
+  t.temp = temp, t.rng = rng, t.logits = logits, t.ld = ld, t.is_bf16 = is_bf16;
+  return masked_argmax<4>(logits, is_bf16, ld, B, V, mask, mask_rows, W, probe, out_idx,
+                          out_logprob, out_probe, workspace, nullptr, s, t);
+}
+
+// g[b, v] = gumbel_noise(rng[b], v): the noise of loqa_masked_argmax_sample's draw,
+// through the same device function (out: f32 [B, V], contiguous)
+__global__ __launch_bounds__(256) void gumbel_noise_kernel(const uint32_t* __restrict__ rng, int V,
+                                                           float* __restrict__ out) {
+  const int v = blockIdx.x * 256 + threadIdx.x;
+  if (v < V) out[(size_t)blockIdx.y * V + v] = gumbel_noise(rng[blockIdx.y], v);
+}
+
+extern "C" int loqa_gumbel_noise(const unsigned* rng, int B, int V, float* out, hipStream_t s) {
+  if (B <= 0 || V <= 0) return B < 0 || V < 0 ? (int)hipErrorInvalidValue : 0;
+  if (!rng || !out || B > 65535) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(gumbel_noise_kernel, dim3((V + 255) / 256, B), dim3(256), 0, s,
+                     (const uint32_t*)rng, V, out);
+  return (int)hipGetLastError();
 }
 
 // ------------------------------------------------- pipelined decode: step I/O
@@ -951,11 +1122,7 @@ extern "C" int loqa_step_publish_lp2(const int* out, const float* lp, const floa
 // own, with exactly the values of the unsharded tensor (tensor-parallel ranks
 // build their slices without materialising the full model). Integer hashing and
 // exact f32 sums: bitwise equal to the CPU path (ops.reference.init_uniform4).
-__device__ __forceinline__ uint32_t fmix32(uint32_t h) {
-  h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-  return h;
-}
-
+// fmix32 (murmur3's finalizer) is defined above, beside the sampling noise.
 __global__ __launch_bounds__(256) void init_uniform4_kernel(bf16_t* __restrict__ out, long long rows,
                                                             int cols, long long ld, long long row0,
                                                             long long col0, uint32_t s, float scale) {

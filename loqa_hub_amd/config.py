@@ -231,6 +231,13 @@ class GPUConfig:
     # most stt_max_initial_timestamp seconds
     stt_timestamps: str = "off"       # off | segment
     stt_max_initial_timestamp: float = 1.0
+    # Whisper's temperature fallback on the gpu backend: a 30 s window whose
+    # text compresses better than stt_compression_ratio_threshold (a repetition
+    # loop) or whose mean token log-probability is below stt_logprob_threshold
+    # is decoded again at the next temperature of the list, sampled on the
+    # device; [0.0] = off (greedy only)
+    stt_temperature: list = field(default_factory=lambda: [0.0])
+    stt_compression_ratio_threshold: float = 2.4
     # relay audio: "fixed" (every chunk is 16 kHz, AudioChunk.sample_rate is
     # ignored: the reference's behaviour) or "relay" (the stream's own rate, one
     # of AUDIO_SAMPLE_RATES; the gpu STT resamples it to 16 kHz on the device,
@@ -388,6 +395,17 @@ class Config:
         if not 0.0 <= self.gpu.stt_max_initial_timestamp <= 30.0:
             raise ConfigError("HUB_STT_MAX_INITIAL_TIMESTAMP must be in [0, 30] seconds: "
                               f"{self.gpu.stt_max_initial_timestamp}")
+        t = self.gpu.stt_temperature
+        if not t or t[0] != 0.0 or any(not 0.0 <= x <= 1.0 for x in t) or \
+                any(b <= a for a, b in zip(t, t[1:])):
+            raise ConfigError("HUB_STT_TEMPERATURE must be a strictly increasing list within "
+                              f"[0, 1] that starts at 0: {t}")
+        if len(t) > 1 and self.gpu.stt_backend != "gpu":
+            raise ConfigError("HUB_STT_TEMPERATURE with a fallback needs HUB_STT_BACKEND=gpu: "
+                              f"{self.gpu.stt_backend}")
+        if not self.gpu.stt_compression_ratio_threshold > 0.0:
+            raise ConfigError("HUB_STT_COMPRESSION_RATIO_THRESHOLD must be > 0: "
+                              f"{self.gpu.stt_compression_ratio_threshold}")
         for c in self.gpu.stt_languages:
             if not re.fullmatch(r"[a-z]{2,3}", c):
                 raise ConfigError(f"invalid HUB_STT_LANGUAGES entry: {c!r}")
@@ -434,6 +452,17 @@ def _strict_float(e, default: float, key: str) -> float:
         return default
     try:
         return float(v)
+    except ValueError:
+        raise ConfigError(f"invalid configuration: invalid {key}: {v}") from None
+
+
+def _float_list(e, default: list, key: str) -> list:
+    """A comma list of numbers ("0,0.2,0.4"); empty / unset: ``default``."""
+    v = env_str(e, "", key).strip()
+    if v == "":
+        return list(default)
+    try:
+        return [float(x) for x in v.split(",")]
     except ValueError:
         raise ConfigError(f"invalid configuration: invalid {key}: {v}") from None
 
@@ -523,6 +552,9 @@ def load(env=None) -> Config:
             stt_logprob_threshold=_strict_float(e, -1.0, "HUB_STT_LOGPROB_THRESHOLD"),
             stt_timestamps=env_str(e, "off", "HUB_STT_TIMESTAMPS").strip().lower(),
             stt_max_initial_timestamp=_strict_float(e, 1.0, "HUB_STT_MAX_INITIAL_TIMESTAMP"),
+            stt_temperature=_float_list(e, [0.0], "HUB_STT_TEMPERATURE"),
+            stt_compression_ratio_threshold=_strict_float(e, 2.4,
+                                                          "HUB_STT_COMPRESSION_RATIO_THRESHOLD"),
             audio_input_rate=env_str(e, "fixed", "HUB_AUDIO_INPUT_RATE").lower(),
             tts_sample_rate=_tts_sample_rate(e),
             tts_backend=env_str(e, "gpu", "HUB_TTS_BACKEND"),

@@ -54,6 +54,7 @@ class PipelineJob:
     error: str = ""
     stt_failed: bool = False
     no_speech: bool = False                 # every window fell to the STT engine's no-speech rule
+    stt_fallback: bool = False              # a window was decoded again at a higher temperature
     # STT engine with timestamps (else None): (start_s, end_s, text) segments in
     # utterance time, and the windows whose last segment was left open
     segments: list | None = None
@@ -151,7 +152,10 @@ class VoicePipeline:
             r.text, r.avg_logprob if self.stt_acoustic is not False else None,
             self.stt_confirm_below, language=r.language,
             language_prob=r.language_prob, no_speech_prob=r.no_speech_prob,
-            segments=r.segments, speech_start_s=r.speech_start_s, speech_end_s=r.speech_end_s)
+            segments=r.segments, speech_start_s=r.speech_start_s, speech_end_s=r.speech_end_s,
+            temperature=max(r.temperatures) if r.temperatures else None,
+            compression_ratio=max(r.compression_ratios) if r.compression_ratios else None)
+        j.stt_fallback = r.fallback_attempts > 0
         j.segments, j.open_segments = r.segments, r.open_segments
         j.no_speech = r.gated_windows > 0 and r.gated_windows == r.windows
 

@@ -16,6 +16,7 @@ import os
 import queue
 import threading
 import time
+import zlib
 from concurrent.futures import FIRST_COMPLETED, Future, ThreadPoolExecutor, wait
 from dataclasses import dataclass, field
 
@@ -50,6 +51,36 @@ MAX_WINDOWS = int(os.environ.get("LOQA_STT_MAX_WINDOWS", "20"))
 PREV_TOKENS = int(os.environ.get("LOQA_STT_PREV_TOKENS", "32"))
 # admissions that may pass a waiting item that does not fit yet (FIFO otherwise)
 HOL_BYPASS = int(os.environ.get("LOQA_STT_HOL_BYPASS", "16"))
+
+
+def compression_ratio(text: str) -> float:
+    """Whisper's repetition measure of a window's text: UTF-8 bytes over their
+    zlib-compressed size (1.0 for empty text). A phrase repeated over and over
+    compresses well: a ratio above ~2.4 marks a repetition loop."""
+    b = text.encode("utf-8")
+    return len(b) / len(zlib.compress(b)) if b else 1.0
+
+
+def needs_fallback(text: str, mean_logprob: float | None, compression_ratio_threshold: float,
+                   logprob_threshold: float) -> bool:
+    """Whisper's ``decode_with_fallback`` test of one decoded window: too
+    repetitive, or its mean token log-probability too low."""
+    if compression_ratio(text) > compression_ratio_threshold:
+        return True
+    return mean_logprob is not None and mean_logprob < logprob_threshold
+
+
+def check_temperatures(temperatures) -> tuple:
+    """The fallback schedule as a tuple of floats: first entry 0, strictly
+    increasing, all within [0, 1]."""
+    try:
+        t = tuple(float(x) for x in temperatures)
+    except (TypeError, ValueError):
+        raise ValueError(f"STT temperatures {temperatures!r}: a sequence of numbers") from None
+    if not t or t[0] != 0.0 or any(not 0.0 <= x <= 1.0 for x in t) or \
+            any(b <= a for a, b in zip(t, t[1:])):
+        raise ValueError(f"STT temperatures {t}: strictly increasing from 0 within [0, 1]")
+    return t
 
 
 def n_windows(n_samples: int, cap: int = MAX_WINDOWS) -> int:
@@ -100,6 +131,14 @@ class STTRequest:
     speech_start_s: float | None = None
     speech_end_s: float | None = None
     open_segments: list | None = None
+    # STTEngine(temperatures=(0, ...)): the key of every random draw of this
+    # request is (sample_seed, window, attempt, token index); None: the engine
+    # assigns one. Per window, the temperature of the attempt that was kept and
+    # its text's compression ratio; the attempts that were discarded in all.
+    sample_seed: int | None = None
+    temperatures: list = field(default_factory=list)
+    compression_ratios: list = field(default_factory=list)
+    fallback_attempts: int = 0
     seq_id: int = -1
     t_done: float = 0.0
     t_enc0: float = 0.0               # encoder start / end, decoder start (perf_counter)
@@ -128,6 +167,7 @@ class STTRequest:
     gated_windows: int = 0            # windows dropped by the no-speech rule
     lp_sum: float = 0.0               # finished windows' log-probability sum / count
     lp_n: int = 0
+    attempt: int = 0                  # index into the engine's temperatures (this window)
 
 
 class STTEngine:
@@ -149,8 +189,21 @@ class STTEngine:
                  token_logprobs: bool = False, sot_probe: bool = False,
                  languages: list[str] | None = None, no_speech: bool = False,
                  no_speech_threshold: float = 0.6, logprob_threshold: float = -1.0,
-                 timestamps: bool = False, max_initial_timestamp: float = 1.0):
+                 timestamps: bool = False, max_initial_timestamp: float = 1.0,
+                 temperatures=(0.0,), compression_ratio_threshold: float = 2.4):
         self.cfg = cfg
+        # temperature fallback (Whisper's decode_with_fallback): a freely decoded
+        # window whose text is too repetitive (compression_ratio_threshold) or too
+        # improbable (logprob_threshold) is decoded again at the next temperature,
+        # its tokens drawn on the device (ops.masked_argmax_sample). (0.0,): off,
+        # the greedy engine as it was.
+        self.temperatures = check_temperatures(temperatures)
+        self.compression_ratio_threshold = float(compression_ratio_threshold)
+        if not self.compression_ratio_threshold >= 0.0:
+            raise ValueError("compression_ratio_threshold must be >= 0")
+        self.fallback = len(self.temperatures) > 1
+        self.seed = int(seed)
+        self._seed_ctr = 0
         # language "auto" (or empty, as the reference passes an empty
         # STT_LANGUAGE through): the language is the argmax over the candidate
         # language tokens at the start-of-transcript position
@@ -174,7 +227,7 @@ class STTEngine:
         self.timestamps = bool(timestamps)
         # the engine stages per-sequence sampling fields (mask_row, probe, with
         # timestamps ts_ctl) and a step returns three results
-        self.row_fields = self.sot_probe or self.timestamps
+        self.row_fields = self.sot_probe or self.timestamps or self.fallback
         token_logprobs = bool(token_logprobs) or self.row_fields
         self.token_logprobs = token_logprobs
         self.device = torch.device(device)
@@ -208,7 +261,8 @@ class STTEngine:
             language = self.lang_codes[0]      # placeholder in ``sot``: fed per request
         if self.row_fields:
             i = self.STEP_FIELDS.index("src")
-            extra = ("mask_row", "probe") + (("ts_ctl",) if self.timestamps else ())
+            extra = ("mask_row", "probe") + (("ts_ctl",) if self.timestamps else ()) + \
+                (("temp", "rng") if self.fallback else ())
             self.step_fields = self.STEP_FIELDS[:i] + extra + self.STEP_FIELDS[i:]
         # start-of-transcript prompt; the language token follows STT_LANGUAGE
         # (the reference passes it to its STT service)
@@ -270,6 +324,9 @@ class STTEngine:
             self.stats.update(no_speech_windows=0, no_speech_utterances=0, languages={})
         if self.timestamps:
             self.stats.update(timestamp_segments=0, open_segments=0)
+        if self.fallback:
+            self.stats.update(fallback_windows=0, fallback_attempts=0)
+        if self.timestamps:
             # the rule state of every cross-attention slot (+ a trash slot, the
             # last, for padding rows), beside ``last_tok``
             self.ts_state = torch.zeros(max_batch + 1, dtype=torch.int32, device=self.device)
@@ -355,7 +412,7 @@ class STTEngine:
     def _layout(self, B_pad: int, T_pad: int) -> StepLayout:
         """``step_layout`` of this engine (a probing one stages two more
         per-sequence fields, ``mask_row`` and ``probe``; a timestamps one those
-        and ``ts_ctl``)."""
+        and ``ts_ctl``; a temperature-fallback one ``temp`` and ``rng`` too)."""
         if not self.row_fields:
             return self.step_layout(B_pad, T_pad, self.max_blocks)
         return StepLayout(step_shapes(self.step_fields, B_pad, T_pad, self.max_blocks),
@@ -515,14 +572,16 @@ class STTEngine:
 
     def _host_meta(self, live: list[STTRequest], B_pad: int, T_pad: int,
                    out: dict | None = None, feeds: list | None = None,
-                   sot: list | None = None, ts_ctl: list | None = None) -> tuple[int, dict]:
+                   sot: list | None = None, ts_ctl: list | None = None,
+                   samp: list | None = None) -> tuple[int, dict]:
         """Host metadata of one step feeding ``feeds`` (default: every
         request's ``feed``); ``out`` = preallocated views (a staging row) to
         fill in place and return. ``sot`` (probing engine): the requests whose
         feed ends in SOT this step (default: ``sot_pending`` and the whole
         remaining prompt fed). ``ts_ctl`` (timestamps engine): the rows' rule
         control words (default: ``_ts_ctl`` of a step that feeds every request's
-        whole remaining feed)."""
+        whole remaining feed). ``samp`` (temperature fallback): the rows'
+        (temperature, random key) (default: ``_samp`` of such a step)."""
         T_enc = self.cfg.n_audio_ctx
         if feeds is None:
             feeds = [r.feed for r in live]
@@ -558,6 +617,17 @@ class STTEngine:
                 host["row_slot"][:n] = [r.slot for r in live]
             host["ts_ctl"][:n] = ts_ctl
             host["ts_ctl"][n:] = 0
+        if self.fallback:
+            if samp is None:
+                samp = [self._samp(r, len(f) < len(r.feed)) for r, f in zip(live, feeds)]
+            if out is None:
+                host["temp"] = np.zeros(B_pad, np.int32)
+                host["rng"] = np.zeros(B_pad, np.int32)
+            # the temperature travels as its f32 bits in the int32 block
+            host["temp"][:n] = np.asarray([t for t, _ in samp], np.float32).view(np.int32)
+            host["temp"][n:] = 0
+            host["rng"][:n] = [k for _, k in samp]
+            host["rng"][n:] = 0
         return max([len(f) for f in feeds] + [1]), host
 
     def _ts_ctl(self, r: STTRequest, partial: bool = False) -> int:
@@ -570,6 +640,23 @@ class STTEngine:
         if partial or r.sot_pending or r.target is not None:
             return 0
         return 1 if not r.tokens else 2
+
+    def _samp(self, r: STTRequest, partial: bool = False) -> tuple[float, int]:
+        """(temperature, random key) of ``r``'s next step, known without tokens
+        like ``_ts_ctl``: (0, 0) - the greedy row - for a prompt chunk, the SOT
+        probe step and a teacher-forced window, else ``_samp_at`` of the token
+        the step samples."""
+        if partial or r.sot_pending or r.target is not None:
+            return 0.0, 0
+        return self._samp_at(r, len(r.tokens))
+
+    def _samp_at(self, r: STTRequest, i: int) -> tuple[float, int]:
+        """(temperature, int32 bits of the random key) of token ``i`` of ``r``'s
+        window at its current attempt; an attempt at temperature 0 is greedy."""
+        T = self.temperatures[r.attempt]
+        if T == 0.0:
+            return 0.0, 0
+        return T, ops.ref.key_i32(ops.ref.sample_key(r.sample_seed, r.win, r.attempt, i))
 
     def _dev(self, host: dict, dst: dict | None = None) -> dict:
         return to_device(host, self.device, dst)
@@ -594,6 +681,16 @@ class STTEngine:
         if not self.row_fields:
             return self._argmax(logits)
         B = logits.shape[0]
+        if self.fallback:
+            # the rules (when on) plus a per-row temperature and random key: a
+            # row at temperature 0 is the greedy one, bit for bit
+            ts = self.timestamps
+            return ops.masked_argmax_sample(
+                logits, self._sup, dev["mask_row"][:B], dev["probe"][:B],
+                dev["ts_ctl"][:B] if ts else None, self.ts_state if ts else None,
+                dev["row_slot"][:B] if ts else None, self.ts_begin if ts else 0,
+                self.ts_count if ts else 0, self.eot if ts else 0, self.max_initial if ts else 0,
+                dev["temp"][:B].view(torch.float32), dev["rng"][:B])
         if self.timestamps:
             # the same three results under Whisper's timestamp rules: the rows'
             # ``ts_ctl`` switches them on, their state is ``ts_state[row_slot]``
@@ -704,11 +801,12 @@ class STTEngine:
         self._graphs_frozen = True
         return n + len(buckets)
 
-    def _step(self, live: list[STTRequest], sot: list | None = None, ts_ctl: list | None = None):
+    def _step(self, live: list[STTRequest], sot: list | None = None, ts_ctl: list | None = None,
+              samp: list | None = None):
         """One decoder step for every live request (its ``feed`` tokens): the
         sampled tokens, with ``token_logprobs`` (tokens, log-probabilities), a
         probing or timestamps engine (tokens, log-probabilities, probed
-        log-probabilities). ``sot``, ``ts_ctl``: see ``_host_meta``."""
+        log-probabilities). ``sot``, ``ts_ctl``, ``samp``: see ``_host_meta``."""
         B = len(live)
         T = sum(len(r.feed) for r in live)
         if self.fast_decode:
@@ -720,7 +818,7 @@ class STTEngine:
                 t0 = time.perf_counter()
                 g = self._graph(B_pad, T_pad, C)
                 hb = self.io.stage(g)
-                self._host_meta(live, B_pad, T_pad, out=hb, sot=sot, ts_ctl=ts_ctl)
+                self._host_meta(live, B_pad, T_pad, out=hb, sot=sot, ts_ctl=ts_ctl, samp=samp)
                 hb["src"].fill(-1)
                 hb["row_slot"].fill(self.io.trash)
                 if self.timestamps:      # the rows' rule state (and last_tok) slots
@@ -732,14 +830,16 @@ class STTEngine:
                 self.stats["host_pre_s"] += t1 - t0
                 self.stats["gpu_wait_s"] += time.perf_counter() - t1
                 return out
-            max_q, host = self._host_meta(live, B_pad, T_pad, sot=sot, ts_ctl=ts_ctl)
+            max_q, host = self._host_meta(live, B_pad, T_pad, sot=sot, ts_ctl=ts_ctl, samp=samp)
             return self._host(self._fast_forward(self._dev(host), max_q, B_pad), B)
+        if self.fallback:
+            return self._eager_step(live, sot, ts_ctl, samp)
         if self.timestamps:
             return self._eager_step(live, sot, ts_ctl)
         return self._eager_step(live, sot) if self.sot_probe else self._eager_step(live)
 
     def _eager_step(self, live: list[STTRequest], sot: list | None = None,
-                    ts_ctl: list | None = None):
+                    ts_ctl: list | None = None, samp: list | None = None):
         """Reference decode path (hipBLASLt GEMMs, eager launches)."""
         T_enc = self.cfg.n_audio_ctx
         toks, pos, slots, cu, ctx, lidx = [], [], [], [0], [], []
@@ -777,6 +877,11 @@ class STTEngine:
                 ts_ctl = [self._ts_ctl(r) for r in live]
             meta["ts_ctl"] = dev(list(ts_ctl), torch.int32)
             meta["row_slot"] = dev([r.slot for r in live], torch.int32)
+        if self.fallback:
+            if samp is None:
+                samp = [self._samp(r) for r in live]
+            meta["temp"] = dev([t for t, _ in samp], torch.float32).view(torch.int32)
+            meta["rng"] = dev([k for _, k in samp], torch.int32)
         return self._host(self._sample(logits, meta))
 
     # ----------------------------------------------------------- admission
@@ -838,6 +943,12 @@ class STTEngine:
             r.language = r.language_prob = r.no_speech_prob = None
             r.no_speech_probs, r.lang_id, r.gated_windows = [], -1, 0
             r.segments = r.open_segments = r.speech_start_s = r.speech_end_s = None
+            r.attempt, r.fallback_attempts = 0, 0
+            r.temperatures, r.compression_ratios = [], []
+            if self.fallback and r.sample_seed is None:
+                # a per-engine counter mixed with the engine seed
+                self._seed_ctr += 1
+                r.sample_seed = ops.ref.sample_key(self.seed, self._seed_ctr, 0, 0)
             if self.timestamps:
                 r.segments, r.open_segments = [], []
             if not r.slots:
@@ -898,6 +1009,13 @@ class STTEngine:
         log-probability among the candidates, log no_speech_prob): record them
         and return the host-known feed that follows SOT. Later windows of an
         utterance keep window 0's language."""
+        if r.attempt > 0:
+            # a fallback attempt runs the SOT step again at temperature 0: the
+            # window's language and no_speech_prob are already recorded
+            r.sot_pending = False
+            post = [r.lang_id] + self.sot[2:]
+            r.chunks.append(post)
+            return post
         if r.win == 0 or r.lang_id < 0:
             r.lang_id = int(idx)
             r.language = self._lang_code.get(r.lang_id)
@@ -925,7 +1043,12 @@ class STTEngine:
                 rest.append(r.feed[n:])
                 r.feed = r.feed[:n]
         live = step
-        if self.timestamps:
+        if self.fallback:
+            nxt = self._step(live, [r.sot_pending and not x for r, x in zip(live, rest)],
+                             [self._ts_ctl(r, bool(x)) for r, x in zip(live, rest)]
+                             if self.timestamps else None,
+                             [self._samp(r, bool(x)) for r, x in zip(live, rest)])
+        elif self.timestamps:
             nxt = self._step(live, [r.sot_pending and not x for r, x in zip(live, rest)],
                              [self._ts_ctl(r, bool(x)) for r, x in zip(live, rest)])
         else:
@@ -978,6 +1101,28 @@ class STTEngine:
             mean_lp = float(np.sum(np.asarray(r.logprobs, np.float64))) / len(r.logprobs)
             gated = r.no_speech_probs[r.win] > self.no_speech_threshold and \
                 mean_lp < self.logprob_threshold
+        if self.fallback:
+            # temperature fallback, on a freely decoded window that the no-speech
+            # rule keeps: too repetitive or too improbable and a higher
+            # temperature left -> this attempt is discarded and the window decoded
+            # again (the last temperature's result stays whatever its quality)
+            T = self.temperatures[r.attempt]
+            text = self.tok.decode(toks).strip()
+            ratio = compression_ratio(text)
+            if r.target is None and not gated and r.attempt + 1 < len(self.temperatures):
+                mean = float(np.sum(np.asarray(r.logprobs, np.float64))) / len(r.logprobs) \
+                    if r.logprobs else None
+                if needs_fallback(text, mean, self.compression_ratio_threshold,
+                                  self.logprob_threshold):
+                    r.fallback_attempts += 1
+                    self.stats["fallback_attempts"] += 1
+                    r.attempt += 1
+                    self._begin_window(r, r.win)
+                    return None
+            r.temperatures.append(T if r.target is None else 0.0)
+            r.compression_ratios.append(ratio)
+            if r.attempt > 0:
+                self.stats["fallback_windows"] += 1
         if gated:
             r.gated_windows += 1
             self.stats["no_speech_windows"] += 1
@@ -995,12 +1140,15 @@ class STTEngine:
         else:
             r.win_texts.append(self.tok.decode(toks).strip())
             r.prev_tokens = (r.prev_tokens + toks)[-max(PREV_TOKENS, 1):]
+        if self.fallback and r.target is None and self.temperatures[r.attempt] > 0.5:
+            r.prev_tokens = []      # Whisper's prompt reset: a hot window does not prompt the next
         if r.logprobs and not gated:
             # fp64 sum of the window's f32 values; -inf (nothing allowed) stays -inf
             r.lp_sum += float(np.sum(np.asarray(r.logprobs, np.float64)))
             r.lp_n += len(r.logprobs)
         if r.win + 1 < r.windows:
             self.stats["long_form_windows"] = self.stats.get("long_form_windows", 0) + 1
+            r.attempt = 0
             self._begin_window(r, r.win + 1)
             return None
         r.t_done = time.perf_counter()

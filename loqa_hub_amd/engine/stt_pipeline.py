@@ -143,11 +143,11 @@ class STTPipeline:
         C = min(eng.cfg.n_text_ctx, -(-ctx // eng.SPLIT_KEYS) * eng.SPLIT_KEYS)
         sot = [r.pl_launched == r.sot_step for r in rows] if eng.sot_probe else None
         if (B_pad, T_pad, C) not in eng._graphs and eng._graphs_frozen:
-            return self._launch_sync(rows, feeds, sot, self._ts_ctl(rows))
+            return self._launch_sync(rows, feeds, sot, self._ts_ctl(rows), self._samp(rows))
         g = eng._graph(B_pad, T_pad, C)
         hb = eng.io.stage(g)
         eng._host_meta(rows, B_pad, T_pad, out=hb, feeds=feeds, sot=sot,
-                       ts_ctl=self._ts_ctl(rows))
+                       ts_ctl=self._ts_ctl(rows), samp=self._samp(rows))
         stage_feeds(hb, feeds, [r.slot for r in rows], eng.io.trash)
         t_r = time.perf_counter()
         rslot = eng.io.replay(g)
@@ -177,7 +177,21 @@ class STTPipeline:
         return [0 if r.target is not None or r.pl_launched < r.prompt_steps - 1 else
                 1 if r.pl_launched == r.prompt_steps - 1 else 2 for r in rows]
 
-    def _launch_sync(self, rows, feeds, sot=None, ts_ctl=None) -> bool:
+    def _samp(self, rows):
+        """A temperature-fallback engine's (temperature, random key) of the rows'
+        next steps, from the launch counts alone like ``_ts_ctl``: the step that
+        samples token i of a freely decoded window takes ``eng._samp_at(r, i)``,
+        every other step (prompt chunks, the SOT probe, teacher forcing) is greedy."""
+        eng = self.eng
+        if not eng.fallback:
+            return None
+        out = []
+        for r in rows:
+            i = r.pl_launched - r.prompt_steps + 1
+            out.append(eng._samp_at(r, i) if r.target is None and i >= 0 else (0.0, 0))
+        return out
+
+    def _launch_sync(self, rows, feeds, sot=None, ts_ctl=None, samp=None) -> bool:
         """Bucket without a captured graph (serving never captures): finish
         what is in flight, then one synchronous step through ``STTEngine._step``."""
         if any(DEV in f for f in feeds):
@@ -185,7 +199,9 @@ class STTPipeline:
         saved = [r.feed for r in rows]
         for r, f in zip(rows, feeds):
             r.feed = f
-        if ts_ctl is not None:
+        if samp is not None:
+            res = self.eng._step(rows, sot, ts_ctl, samp)
+        elif ts_ctl is not None:
             res = self.eng._step(rows, sot, ts_ctl)
         else:
             res = self.eng._step(rows, sot) if sot is not None else self.eng._step(rows)

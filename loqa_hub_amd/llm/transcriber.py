@@ -39,6 +39,11 @@ class TranscriptionResult:
     segments: list | None = None
     speech_start_s: float | None = None
     speech_end_s: float | None = None
+    # HUB_STT_TEMPERATURE with a fallback (gpu backend; else None): the highest
+    # temperature any 30 s window was kept at and the largest compression ratio
+    # of the windows' texts
+    temperature: float | None = None
+    compression_ratio: float | None = None
 
 
 @dataclass
@@ -106,7 +111,9 @@ def to_transcription_result(raw: str, avg_logprob: float | None = None,
                             language: str | None = None, language_prob: float | None = None,
                             no_speech_prob: float | None = None, segments: list | None = None,
                             speech_start_s: float | None = None,
-                            speech_end_s: float | None = None) -> TranscriptionResult:
+                            speech_end_s: float | None = None,
+                            temperature: float | None = None,
+                            compression_ratio: float | None = None) -> TranscriptionResult:
     """``avg_logprob`` (the on-device Whisper decode's mean token
     log-probability): the confidence is the geometric-mean token probability
     ``min(1, exp(avg_logprob))`` instead of the text heuristic, and a
@@ -115,10 +122,12 @@ def to_transcription_result(raw: str, avg_logprob: float | None = None,
     ``language`` / ``language_prob`` / ``no_speech_prob``: what the decoder read
     at the start-of-transcript position, carried as they are; so are
     ``segments`` / ``speech_start_s`` / ``speech_end_s`` of a decode with
-    timestamps (their texts are the decoder's, before the wake-word cut)."""
+    timestamps (their texts are the decoder's, before the wake-word cut), and
+    ``temperature`` / ``compression_ratio`` of a decode with temperature fallback."""
     p = post_process_transcription(raw)
     probe = dict(language=language, language_prob=language_prob, no_speech_prob=no_speech_prob,
-                 segments=segments, speech_start_s=speech_start_s, speech_end_s=speech_end_s)
+                 segments=segments, speech_start_s=speech_start_s, speech_end_s=speech_end_s,
+                 temperature=temperature, compression_ratio=compression_ratio)
     if avg_logprob is None:
         return TranscriptionResult(p.cleaned_text, p.confidence_estimate, p.wake_word_detected,
                                    p.wake_word_variant, p.needs_confirmation, **probe)

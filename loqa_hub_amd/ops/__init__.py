@@ -405,6 +405,80 @@ def masked_argmax_timestamps(logits: torch.Tensor, mask: torch.Tensor | None,
     return out, lp, plp
 
 
+def masked_argmax_sample(logits: torch.Tensor, mask: torch.Tensor | None,
+                         mask_rows: torch.Tensor | None, probe: torch.Tensor,
+                         ts_ctl: torch.Tensor | None, ts_state: torch.Tensor | None,
+                         row_slot: torch.Tensor | None, ts_begin: int, ts_count: int, eot: int,
+                         max_initial: int, temp: torch.Tensor, rng: torch.Tensor
+                         ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``masked_argmax_timestamps`` with temperature sampling per row, drawn on
+    the device. ``temp`` float32 [B], finite and >= 0; ``rng`` int32 [B], the bits
+    of each row's uint32 key (``ops.reference.sample_key``). A row with ``temp[b]
+    == 0`` is ``masked_argmax_timestamps``'s bit for bit. A row with ``temp[b] >
+    0`` draws its token by Gumbel-max over ``logits / temp`` among what the mask
+    and the rules leave (the mass rule is applied at temperature 1 first, as
+    Whisper filters its logits before sampling) with the counter-based noise
+    ``gumbel_noise(rng[b], column)``; its log-probability is at temperature 1.
+    ``ts_ctl`` None: every row is rule-off (``ts_state``, ``row_slot`` and the
+    layout arguments are ignored) - ``masked_argmax_logprob_probe`` with the
+    draw. A bad ``temp`` is a ValueError when it is a host tensor; on the device
+    a row whose ``temp`` is not > 0 (NaN included) is greedy. Returns (int32 [B],
+    float32 [B], float32 [B])."""
+    assert logits.dim() == 2 and logits.stride(-1) == 1
+    B, V = logits.shape
+    rows = (probe, temp, rng) if ts_ctl is None else (probe, temp, rng, ts_ctl, row_slot)
+    for t in rows:
+        assert t.is_contiguous() and t.numel() == B and t.device == logits.device
+        assert t.dtype == (torch.float32 if t is temp else torch.int32)
+    if temp.device.type == "cpu" and B:
+        if not bool(torch.isfinite(temp).all()) or float(temp.min()) < 0:
+            raise ValueError("temp must be finite and >= 0")
+    if probe.device.type == "cpu" and B and int(probe.max()) >= V:
+        raise ValueError(f"probe column {int(probe.max())} is outside the {V} logits")
+    if ts_ctl is None:
+        if not _gpu(logits):
+            return ref.masked_argmax_sample(logits, mask, mask_rows, probe, None, None, None, 0, 0,
+                                            0, 0, temp, rng)
+        slots = 0
+    else:
+        assert ts_state.dtype == torch.int32 and ts_state.is_contiguous() and ts_state.dim() == 1
+        assert ts_state.device == logits.device
+        if not (0 <= eot <= ts_begin and ts_count >= 1 and ts_begin + ts_count <= V
+                and max_initial >= 0):
+            raise ValueError(f"timestamp layout eot={eot} ts_begin={ts_begin} ts_count={ts_count} "
+                             f"max_initial={max_initial} does not fit {V} logits")
+        max_initial = min(int(max_initial), ts_count - 1)
+        if probe.device.type == "cpu" and B:
+            ruled = row_slot[(ts_ctl == 1) | (ts_ctl == 2)]
+            assert ruled.numel() == ruled.unique().numel(), "two ruled rows share a state slot"
+            assert not ruled.numel() or (0 <= int(ruled.min())
+                                         and int(ruled.max()) < ts_state.numel())
+        if not _gpu(logits):
+            return ref.masked_argmax_sample(logits, mask, mask_rows, probe, ts_ctl, ts_state,
+                                            row_slot, ts_begin, ts_count, eot, max_initial, temp,
+                                            rng)
+        slots = ts_state.numel()
+    head, out, (lp, plp), ws = _argmax_args(logits, mask, mask_rows, 2, 8)   # 64-byte records
+    check(kernels().loqa_masked_argmax_sample(
+        *head, ptr(probe), ptr(ts_ctl), ptr(ts_state), ptr(row_slot), slots, ts_begin, ts_count,
+        eot, max_initial, ptr(temp), ptr(rng), ptr(out), ptr(lp), ptr(plp), ptr(ws),
+        stream_ptr(logits)), "masked_argmax_sample")
+    return out, lp, plp
+
+
+def gumbel_noise(rng: torch.Tensor, V: int) -> torch.Tensor:
+    """float32 [B, V]: ``-log(-log(u))`` of ``masked_argmax_sample``'s counter-based
+    uniforms for the row keys ``rng`` (int32 [B]) - on the GPU written by the
+    device function the sampling kernel draws with."""
+    assert rng.dtype == torch.int32 and rng.is_contiguous() and rng.dim() == 1 and V >= 1
+    if not _gpu(rng):
+        return ref.gumbel_noise(rng, V)
+    out = torch.empty(rng.numel(), V, dtype=torch.float32, device=rng.device)
+    check(kernels().loqa_gumbel_noise(ptr(rng), rng.numel(), V, ptr(out), stream_ptr(rng)),
+          "gumbel_noise")
+    return out
+
+
 # -------------------------------------------------------------------- audio
 def pcm16_to_f32_sumsq(pcm: torch.Tensor, offsets: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     """pcm: int16 [N] (concatenated segments), offsets: int64 [S+1].

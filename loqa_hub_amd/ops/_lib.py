@@ -173,6 +173,15 @@ _KERNEL_SIGS = {
                               #  eot, max_initial, out_idx, out_logprob, out_probe, workspace, stream)
                               c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                               c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "loqa_masked_argmax_sample": [c_void_p, c_int, c_ll, c_int, c_int, c_void_p, c_void_p, c_int,
+                                  # (..., probe, ts_ctl, ts_state, row_slot, slots, ts_begin,
+                                  #  ts_count, eot, max_initial, temp, rng, out_idx, out_logprob,
+                                  #  out_probe, workspace, stream)
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                  c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p],
+    # (rng, B, V, out, stream)
+    "loqa_gumbel_noise": [c_void_p, c_int, c_int, c_void_p, c_void_p],
 }
 
 # (argtypes, restype) of the custom all-reduce entry points (in the kernels library)

@@ -264,29 +264,152 @@ def masked_argmax_timestamps(logits, mask, mask_rows, probe, ts_ctl, ts_state, r
             continue
         slot = int(row_slot[b])
         word = int(ts_state[slot])
-        text_ok, lo, hi = ts_allowed(word, ctl, ts_count, max_initial)
-        if mask is not None:
-            okx = unpack_mask(mask[int(mask_rows[b]) if mask_rows is not None else b], V).clone()
-        else:
-            okx = torch.ones(V, dtype=torch.bool)
-        okx[ts_begin:] = False
-        okx[: (ts_begin, eot, 0)[text_ok]] = False
-        okt = torch.zeros(V, dtype=torch.bool)
-        okt[ts_begin + lo: ts_begin + hi + 1] = True
-        xx = x[b].masked_fill(~okx, ninf)
-        xt_ = x[b].masked_fill(~okt, ninf)
-        any_x, any_t = bool(okx.any()), bool(okt.any())
-        lse_a = torch.logsumexp(x[b].masked_fill(~(okx | okt), ninf), dim=-1)
-        lse_t = torch.logsumexp(xt_, dim=-1)
-        fire = any_t and (not any_x or bool(ts_mass_rule(lse_t, lse_a, xx.max())))
-        if not (any_x or any_t):
+        okx, okt, fire, lse_a, lse_t = _ts_classes(x[b], mask, mask_rows, b, word, ctl, ts_begin,
+                                                   ts_count, eot, max_initial)
+        if not (bool(okx.any()) or bool(okt.any())):
             idx[b], lp[b] = -1, ninf
             continue
-        row, lse = (xt_, lse_t) if fire else (xx, lse_a)
+        row, lse = (x[b].masked_fill(~okt, ninf), lse_t) if fire else \
+            (x[b].masked_fill(~okx, ninf), lse_a)
         w = int(row.argmax())
         idx[b] = w
         lp[b] = row[w] - lse if row[w] != ninf else ninf
         ts_state[slot] = ts_state_next(word, ctl, w, ts_begin)
+    return idx, lp, plp
+
+
+def _ts_classes(xb, mask, mask_rows, b, word, ctl, ts_begin, ts_count, eot, max_initial):
+    """A ruled row's two classes and the mass rule: (``okx`` = the mask's
+    columns below ``ts_begin`` that the rules leave, ``okt`` = the allowed
+    timestamp columns, the rule fires, logsumexp over both, over ``okt``)."""
+    V = xb.shape[0]
+    ninf = float("-inf")
+    text_ok, lo, hi = ts_allowed(word, ctl, ts_count, max_initial)
+    if mask is not None:
+        okx = unpack_mask(mask[int(mask_rows[b]) if mask_rows is not None else b], V).clone()
+    else:
+        okx = torch.ones(V, dtype=torch.bool)
+    okx[ts_begin:] = False
+    okx[: (ts_begin, eot, 0)[text_ok]] = False
+    okt = torch.zeros(V, dtype=torch.bool)
+    okt[ts_begin + lo: ts_begin + hi + 1] = True
+    xx = xb.masked_fill(~okx, ninf)
+    any_x, any_t = bool(okx.any()), bool(okt.any())
+    lse_a = torch.logsumexp(xb.masked_fill(~(okx | okt), ninf), dim=-1)
+    lse_t = torch.logsumexp(xb.masked_fill(~okt, ninf), dim=-1)
+    fire = any_t and (not any_x or bool(ts_mass_rule(lse_t, lse_a, xx.max())))
+    return okx, okt, fire, lse_a, lse_t
+
+
+# Temperature sampling (MODE 4 of the row scan): counter-based Gumbel noise in
+# integer arithmetic that the device reproduces exactly, and the draw.
+_M32 = 0xFFFFFFFF
+
+
+def fmix32(h: int) -> int:
+    """murmur3's 32-bit finalizer on a Python int (``_fmix32`` on tensors)."""
+    h &= _M32
+    h ^= h >> 16
+    h = (h * 0x85EBCA6B) & _M32
+    h ^= h >> 13
+    h = (h * 0xC2B2AE35) & _M32
+    return h ^ (h >> 16)
+
+
+def sample_key(seed: int, window: int, attempt: int, token_index: int) -> int:
+    """The uint32 row key of one sampled token: an ``fmix32`` chain over (request
+    seed, 30 s window, fallback attempt, index of the token in the window). It
+    names the draw, so it is the same in any batch, bucket or pipeline depth."""
+    h = fmix32((int(seed) + 0x9E3779B9) & _M32)
+    for x in (window, attempt, token_index):
+        h = fmix32(((h ^ (int(x) & _M32)) + 0x9E3779B9) & _M32)
+    return h
+
+
+def key_i32(key: int) -> int:
+    """A uint32 key as the int32 with the same bits (the step field's type)."""
+    key &= _M32
+    return key - (1 << 32) if key >= (1 << 31) else key
+
+
+def gumbel_hash(rng: torch.Tensor, V: int) -> torch.Tensor:
+    """h[b, v] = fmix32(rng[b] ^ fmix32(v + 0x9E3779B9)) as int64 in [0, 2^32);
+    ``rng``: int32 [B] (the bits of a uint32 key)."""
+    key = (rng.to(torch.int64).cpu() & _M32)[:, None]
+    col = _fmix32((torch.arange(V, dtype=torch.int64)[None, :] + 0x9E3779B9) & _M32)
+    return _fmix32(key ^ col)
+
+
+def gumbel_uniform(h: torch.Tensor) -> torch.Tensor:
+    """u = (2 (h >> 9) + 1) / 2^24 of a 32-bit hash: an exact float32 in
+    [2^-24, 1 - 2^-24], so ``-log(-log(u))`` is finite."""
+    return (2 * (h.to(torch.int64) >> 9) + 1).to(torch.float32) * (1.0 / 16777216.0)
+
+
+def gumbel_noise(rng: torch.Tensor, V: int) -> torch.Tensor:
+    """g[b, v] = -log(-log(u)) in float32 for ``u = gumbel_uniform(gumbel_hash(rng,
+    V))``: the CPU engine's noise. The device takes the same ``u`` through its own
+    ``logf``, so its ``g`` agrees to a few ulp, not bit for bit."""
+    u = gumbel_uniform(gumbel_hash(rng, V))
+    return -torch.log(-torch.log(u))
+
+
+def masked_argmax_sample(logits, mask, mask_rows, probe, ts_ctl, ts_state, row_slot, ts_begin,
+                         ts_count, eot, max_initial, temp, rng, noise=None):
+    """``masked_argmax_timestamps`` with a per-row temperature ``temp`` (float32
+    [B]) and random key ``rng`` (int32 [B]). ``temp[b] == 0``: that op's row
+    (``ts_ctl`` None: ``masked_argmax_logprob_probe``'s, every row rule-off).
+    ``temp[b] > 0``: the row draws by Gumbel-max, the winner maximises
+    ``x + T * g`` (fp64, rounded once to float32: the device's fmaf) over the
+    allowed timestamps when the mass rule - evaluated at temperature 1, as
+    Whisper filters the logits before it samples - fires, else over every
+    allowed column; its log-probability is at temperature 1 over the same set.
+    ``noise`` (float32 [B, V]): ``g``, default ``gumbel_noise(rng, V)``."""
+    x = logits.float()
+    B, V = x.shape
+    ninf = float("-inf")
+    T = temp.float().cpu()
+    sampling = T > 0
+    if ts_ctl is None:
+        idx, lp, plp = masked_argmax_logprob_probe(logits, mask, mask_rows, probe)
+        ctl_all = torch.zeros(B, dtype=torch.int32)
+    else:
+        ctl_all = ts_ctl.clone()
+        ctl_all[~((ctl_all == 1) | (ctl_all == 2))] = 0
+        greedy_ctl = ctl_all.clone()
+        greedy_ctl[sampling] = 0          # the greedy pass leaves their state alone
+        idx, lp, plp = masked_argmax_timestamps(logits, mask, mask_rows, probe, greedy_ctl,
+                                                ts_state, row_slot, ts_begin, ts_count, eot,
+                                                max_initial)
+        max_initial = min(int(max_initial), ts_count - 1)
+    if not bool(sampling.any()):
+        return idx, lp, plp
+    g = gumbel_noise(rng, V) if noise is None else noise.float().cpu()
+    key = (x.double() + T.double()[:, None] * g.double()).float()
+    for b in range(B):
+        if not bool(sampling[b]):
+            continue
+        ctl = int(ctl_all[b])
+        if ctl:
+            slot = int(row_slot[b])
+            word = int(ts_state[slot])
+            okx, okt, fire, _, _ = _ts_classes(x[b], mask, mask_rows, b, word, ctl, ts_begin,
+                                               ts_count, eot, max_initial)
+            allowed = okt if fire else (okx | okt)
+        elif mask is not None:
+            allowed = unpack_mask(mask[int(mask_rows[b]) if mask_rows is not None else b], V)
+        else:
+            allowed = torch.ones(V, dtype=torch.bool)
+        cols = allowed.nonzero()[:, 0]
+        if not cols.numel():
+            idx[b], lp[b] = -1, ninf
+            continue
+        w = int(cols[key[b, cols].argmax()])      # the first maximum: the lowest column
+        idx[b] = w
+        lse = torch.logsumexp(x[b].masked_fill(~allowed, ninf), dim=-1)
+        lp[b] = x[b, w] - lse if x[b, w] != ninf else ninf
+        if ctl:
+            ts_state[slot] = ts_state_next(word, ctl, w, ts_begin)
     return idx, lp, plp
 
 

@@ -89,7 +89,7 @@ class GPUVoiceProcessor:
         pipeline.batch_window, pipeline.max_batch = batch_window, max_batch
         self.stats = {"utterances": 0, "errors": 0, "bridge_sessions": 0, "bridge_ack": 0,
                       "bridge_fallback": 0, "interrupted": 0, "stt_low_confidence": 0,
-                      "stt_no_speech": 0,
+                      "stt_no_speech": 0, "stt_fallback": 0,
                       "progressive": 0, "first_audio_ms_sum": 0.0, "first_audio_n": 0}
         # a list that collects every finished PipelineJob (phase timestamps for
         # a benchmark's per-phase breakdown); None: not collected
@@ -198,6 +198,11 @@ class GPUVoiceProcessor:
             if tr.no_speech_prob is not None:    # the engine reads the SOT logits
                 r.metrics["stt"].update(language=tr.language, language_prob=tr.language_prob,
                                         no_speech_prob=tr.no_speech_prob)
+            if tr.temperature is not None:       # the engine decodes with temperature fallback
+                r.metrics["stt"].update(temperature=tr.temperature,
+                                        compression_ratio=tr.compression_ratio)
+            if getattr(j, "stt_fallback", False):   # some window was decoded again
+                self.stats["stt_fallback"] += 1
             if j.no_speech:                      # dropped by the no-speech rule: no LLM pass
                 self.stats["stt_no_speech"] += 1
             below = CONFIRMATION_THRESHOLD      # the heuristic keeps the reference's threshold

@@ -55,6 +55,13 @@ LABELS.update({
         f"argmax + timestamp rules, {'bf16' if bf else 'f32'}, {'V <= 8192' if single else 'chunked'}"
     for bf in (True, False) for single in (True, False)})
 LABELS["argmax_finalize_kernel<3, TsArgs>"] = "argmax finalize, mode 3"
+# MODE 4 (temperature sampling beside the rules): a trailing SampleArgs
+LABELS.update({
+    f"masked_argmax_kernel<{str(bf).lower()}, {str(single).lower()}, 4, SampleArgs>":
+        f"argmax + rules + sampling, {'bf16' if bf else 'f32'}, {'V <= 8192' if single else 'chunked'}"
+    for bf in (True, False) for single in (True, False)})
+LABELS["argmax_finalize_kernel<4, SampleArgs>"] = "argmax finalize, mode 4"
+LABELS["gumbel_noise_kernel"] = "Gumbel noise (test export)"
 PAT = {"V": r"VGPRs: (\d+)", "A": r"AGPRs: (\d+)", "occ": r"Occupancy \[waves/SIMD\]: (\d+)",
        "LDS": r"LDS Size \[bytes/block\]: (\d+)", "spill": r"VGPRs Spill: (\d+)"}
 
