@@ -238,6 +238,13 @@ class GPUConfig:
     # device; [0.0] = off (greedy only)
     stt_temperature: list = field(default_factory=lambda: [0.0])
     stt_compression_ratio_threshold: float = 2.4
+    # word timestamps on the gpu backend (with or without stt_timestamps): the
+    # decoder keeps the cross-attention queries of the alignment heads and every
+    # kept 30 s window is aligned on the device (dynamic time warping);
+    # stt_alignment_heads = "layer:head,..." (at most 32; empty: the checkpoint's
+    # generation config, else every head of the upper half of the decoder layers)
+    stt_word_timestamps: str = "off"  # off | on
+    stt_alignment_heads: str = ""
     # relay audio: "fixed" (every chunk is 16 kHz, AudioChunk.sample_rate is
     # ignored: the reference's behaviour) or "relay" (the stream's own rate, one
     # of AUDIO_SAMPLE_RATES; the gpu STT resamples it to 16 kHz on the device,
@@ -392,6 +399,16 @@ class Config:
         if self.gpu.stt_timestamps == "segment" and self.gpu.stt_backend != "gpu":
             raise ConfigError("HUB_STT_TIMESTAMPS=segment needs HUB_STT_BACKEND=gpu: "
                               f"{self.gpu.stt_backend}")
+        if self.gpu.stt_word_timestamps not in ("off", "on"):
+            raise ConfigError("invalid HUB_STT_WORD_TIMESTAMPS (off | on): "
+                              f"{self.gpu.stt_word_timestamps}")
+        if self.gpu.stt_word_timestamps == "on" and self.gpu.stt_backend != "gpu":
+            raise ConfigError("HUB_STT_WORD_TIMESTAMPS=on needs HUB_STT_BACKEND=gpu: "
+                              f"{self.gpu.stt_backend}")
+        if self.gpu.stt_alignment_heads:
+            if not re.fullmatch(r"\d+:\d+(,\d+:\d+){0,31}", self.gpu.stt_alignment_heads):
+                raise ConfigError("HUB_STT_ALIGNMENT_HEADS must be 'layer:head,...' (at most 32): "
+                                  f"{self.gpu.stt_alignment_heads}")
         if not 0.0 <= self.gpu.stt_max_initial_timestamp <= 30.0:
             raise ConfigError("HUB_STT_MAX_INITIAL_TIMESTAMP must be in [0, 30] seconds: "
                               f"{self.gpu.stt_max_initial_timestamp}")
@@ -553,6 +570,8 @@ def load(env=None) -> Config:
             stt_timestamps=env_str(e, "off", "HUB_STT_TIMESTAMPS").strip().lower(),
             stt_max_initial_timestamp=_strict_float(e, 1.0, "HUB_STT_MAX_INITIAL_TIMESTAMP"),
             stt_temperature=_float_list(e, [0.0], "HUB_STT_TEMPERATURE"),
+            stt_word_timestamps=env_str(e, "off", "HUB_STT_WORD_TIMESTAMPS").strip().lower(),
+            stt_alignment_heads="".join(env_str(e, "", "HUB_STT_ALIGNMENT_HEADS").split()),
             stt_compression_ratio_threshold=_strict_float(e, 2.4,
                                                           "HUB_STT_COMPRESSION_RATIO_THRESHOLD"),
             audio_input_rate=env_str(e, "fixed", "HUB_AUDIO_INPUT_RATE").lower(),

@@ -59,6 +59,9 @@ class PipelineJob:
     # utterance time, and the windows whose last segment was left open
     segments: list | None = None
     open_segments: list | None = None
+    # STT engine with word timestamps (else None): (start_s, end_s, word,
+    # probability) in utterance time
+    words: list | None = None
     llm_steps: int = 0                      # decode steps the intent parse sampled in
     t: dict = field(default_factory=dict)   # stage timestamps (perf_counter)
 
@@ -154,9 +157,11 @@ class VoicePipeline:
             language_prob=r.language_prob, no_speech_prob=r.no_speech_prob,
             segments=r.segments, speech_start_s=r.speech_start_s, speech_end_s=r.speech_end_s,
             temperature=max(r.temperatures) if r.temperatures else None,
-            compression_ratio=max(r.compression_ratios) if r.compression_ratios else None)
+            compression_ratio=max(r.compression_ratios) if r.compression_ratios else None,
+            words=r.words)
         j.stt_fallback = r.fallback_attempts > 0
         j.segments, j.open_segments = r.segments, r.open_segments
+        j.words = r.words
         j.no_speech = r.gated_windows > 0 and r.gated_windows == r.windows
 
     def build_request(self, j: PipelineJob) -> GenRequest | None:

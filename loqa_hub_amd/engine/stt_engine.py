@@ -31,6 +31,7 @@ from .batching import join_futures, plan_step
 from .kv_cache import PagedKVCache
 from .step_io import StepIO, StepLayout, decode_buckets, fill_meta, step_shapes, to_device
 from .stt_segments import cut_window, text_tokens, utterance_segments
+from .stt_words import utterance_words, window_words
 from .tokenizer import (SyntheticTimestampTokenizer, SyntheticTokenizer, SyntheticWhisperTokenizer,
                         get_tokenizer)
 
@@ -139,6 +140,15 @@ class STTRequest:
     temperatures: list = field(default_factory=list)
     compression_ratios: list = field(default_factory=list)
     fallback_attempts: int = 0
+    # STTEngine(word_timestamps=True) (None with the feature off): ``words`` =
+    # (start_s, end_s, word, probability) in utterance time (window w adds 30 w s,
+    # clamped to the utterance's duration; probability None when teacher-forced),
+    # ``word_segments`` the index of each word's segment (with timestamps off: its
+    # window), ``token_frames`` per kept window the raw ``tok_frame`` of its text
+    # tokens (and of a sampled EOT), 20 ms frames from the window's start
+    words: list | None = None
+    word_segments: list | None = None
+    token_frames: list = field(default_factory=list)
     seq_id: int = -1
     t_done: float = 0.0
     t_enc0: float = 0.0               # encoder start / end, decoder start (perf_counter)
@@ -168,6 +178,7 @@ class STTRequest:
     lp_sum: float = 0.0               # finished windows' log-probability sum / count
     lp_n: int = 0
     attempt: int = 0                  # index into the engine's temperatures (this window)
+    prompt_len: int = 0               # tokens fed before the window's first sampled token
 
 
 class STTEngine:
@@ -190,7 +201,8 @@ class STTEngine:
                  languages: list[str] | None = None, no_speech: bool = False,
                  no_speech_threshold: float = 0.6, logprob_threshold: float = -1.0,
                  timestamps: bool = False, max_initial_timestamp: float = 1.0,
-                 temperatures=(0.0,), compression_ratio_threshold: float = 2.4):
+                 temperatures=(0.0,), compression_ratio_threshold: float = 2.4,
+                 word_timestamps: bool = False, alignment_heads=None):
         self.cfg = cfg
         # temperature fallback (Whisper's decode_with_fallback): a freely decoded
         # window whose text is too repetitive (compression_ratio_threshold) or too
@@ -209,6 +221,7 @@ class STTEngine:
         # language tokens at the start-of-transcript position
         language = (language or "auto").strip().lower() or "auto"
         self.auto_language = language == "auto"
+        self.language = None if self.auto_language else language
         # no_speech: Whisper's rule drops a freely decoded window whose
         # no_speech_prob > no_speech_threshold and whose mean token
         # log-probability < logprob_threshold
@@ -228,7 +241,8 @@ class STTEngine:
         # the engine stages per-sequence sampling fields (mask_row, probe, with
         # timestamps ts_ctl) and a step returns three results
         self.row_fields = self.sot_probe or self.timestamps or self.fallback
-        token_logprobs = bool(token_logprobs) or self.row_fields
+        # (word timestamps report a probability per word: they record them too)
+        token_logprobs = bool(token_logprobs) or self.row_fields or bool(word_timestamps)
         self.token_logprobs = token_logprobs
         self.device = torch.device(device)
         if self.device.type == "cuda" and self.device.index is None:
@@ -330,6 +344,19 @@ class STTEngine:
             # the rule state of every cross-attention slot (+ a trash slot, the
             # last, for padding rows), beside ``last_tok``
             self.ts_state = torch.zeros(max_batch + 1, dtype=torch.int32, device=self.device)
+        # word timestamps (Whisper's find_alignment without a second decoder
+        # pass): every decoder step ends with ops.align_record, which keeps the
+        # alignment heads' cross-attention queries per (slot, position); a kept
+        # window is aligned in _finish (ops.align_scores / align_cost / dtw).
+        # Record and alignment run on this engine's one stream.
+        self.align = None
+        if word_timestamps:
+            if isinstance(alignment_heads, (list, tuple)):
+                alignment_heads = ",".join(f"{int(l)}:{int(h)}" for l, h in alignment_heads)
+            heads = ops.ref.alignment_heads(cfg.dec_layers, cfg.n_heads, alignment_heads,
+                                            getattr(self.tok, "generation_config", None))
+            self.align = ops.AlignStore(cfg, heads, max_batch + 1, self.device)
+            self.stats.update(aligned_windows=0, aligned_words=0)
         self.max_batch = max_batch
         self.fast_decode = fast_decode
         # fused-epilogue decoder GEMMs (8 launches per layer) for Mpad <= 64
@@ -617,6 +644,9 @@ class STTEngine:
                 host["row_slot"][:n] = [r.slot for r in live]
             host["ts_ctl"][:n] = ts_ctl
             host["ts_ctl"][n:] = 0
+        if self.align is not None and out is None:
+            host["row_slot"] = np.full(B_pad, self.max_batch, np.int32)
+            host["row_slot"][:n] = [r.slot for r in live]
         if self.fallback:
             if samp is None:
                 samp = [self._samp(r, len(f) < len(r.feed)) for r, f in zip(live, feeds)]
@@ -711,18 +741,19 @@ class STTEngine:
 
     def _fast_forward(self, dev: dict, max_q: int, B_pad: int, ctx: int | None = None):
         ns = self._self_splits(ctx)
+        al = (self.align, dev["row_slot"]) if self.align is not None else None
         if self.fused and dev["tokens"].numel() <= 64:
             logits = decode_step_fused(self.model, dev["tokens"], dev["positions"], dev["slots"],
                                        dev["cu_q"], dev["ctx_lens"], dev["block_tables"], max_q,
                                        self.kv.k, self.kv.v, self.xkv, dev["enc_starts"],
                                        dev["enc_lens"], dev["logit_idx"], self.ws, self.scratch,
-                                       ns, self.SPLIT_KEYS, self.cross_split_keys)
+                                       ns, self.SPLIT_KEYS, self.cross_split_keys, align=al)
             return self._sample(logits[:B_pad, : self.cfg.vocab_size], dev)
         logits = decode_step_fast(self.model, dev["tokens"], dev["positions"], dev["slots"],
                                   dev["cu_q"], dev["ctx_lens"], dev["block_tables"], max_q,
                                   self.kv.k, self.kv.v, self.xkv, dev["enc_starts"],
                                   dev["enc_lens"], dev["logit_idx"], self.ws, ns,
-                                  self.SPLIT_KEYS)
+                                  self.SPLIT_KEYS, align=al)
         return self._sample(logits[:B_pad, : self.cfg.vocab_size], dev)
 
     def _graph(self, B_pad: int, T_pad: int, ctx: int) -> dict:
@@ -821,7 +852,8 @@ class STTEngine:
                 self._host_meta(live, B_pad, T_pad, out=hb, sot=sot, ts_ctl=ts_ctl, samp=samp)
                 hb["src"].fill(-1)
                 hb["row_slot"].fill(self.io.trash)
-                if self.timestamps:      # the rows' rule state (and last_tok) slots
+                if self.timestamps or self.align is not None:
+                    # the rows' rule state / query store (and last_tok) slots
                     hb["row_slot"][:B] = [r.slot for r in live]
                 t1 = time.perf_counter()
                 rslot = self.io.replay(g)
@@ -862,10 +894,13 @@ class STTEngine:
         dev = lambda a, dt: torch.tensor(a, dtype=dt).to(self.device, non_blocking=True)
         enc_starts = dev([r.slot * T_enc for r in live], torch.int32)
         enc_lens = dev([T_enc] * len(live), torch.int32)
+        al = (self.align, dev([r.slot for r in live], torch.int32)) \
+            if self.align is not None else None
         logits = self.model.decode_step(
             dev(toks, torch.int32), dev(pos, torch.int32), dev(slots, torch.int32),
             dev(cu, torch.int32), dev(ctx, torch.int32), dev(bt, torch.int32), max_q, max_ctx,
-            self.kv.k, self.kv.v, self.xkv, enc_starts, enc_lens, dev(lidx, torch.int64), self.ws)
+            self.kv.k, self.kv.v, self.xkv, enc_starts, enc_lens, dev(lidx, torch.int64), self.ws,
+            align=al)
         if not self.row_fields:
             return self._host(self._argmax(logits))
         if sot is None:
@@ -945,6 +980,8 @@ class STTEngine:
             r.segments = r.open_segments = r.speech_start_s = r.speech_end_s = None
             r.attempt, r.fallback_attempts = 0, 0
             r.temperatures, r.compression_ratios = [], []
+            r.token_frames = []
+            r.words, r.word_segments = ([], []) if self.align is not None else (None, None)
             if self.fallback and r.sample_seed is None:
                 # a per-engine counter mixed with the engine seed
                 self._seed_ctr += 1
@@ -979,6 +1016,7 @@ class STTEngine:
         if w > 0 and self.sop is not None and r.prev_tokens and PREV_TOKENS > 0:
             prompt = [self.sop] + r.prev_tokens[-PREV_TOKENS:]
         r.tokens, r.step, r.feed = [], 0, prompt + list(self.sot)
+        r.prompt_len = len(r.feed)
         r.logprobs = []
         c = len(self.sot)
         r.sot_step, r.sot_pending = -1, False
@@ -1123,6 +1161,7 @@ class STTEngine:
             r.compression_ratios.append(ratio)
             if r.attempt > 0:
                 self.stats["fallback_windows"] += 1
+        seg_of = None
         if gated:
             r.gated_windows += 1
             self.stats["no_speech_windows"] += 1
@@ -1130,6 +1169,14 @@ class STTEngine:
         elif segs is not None:
             out = utterance_segments(segs, r.win, r.n_samples / 16000.0,
                                      lambda t: self.tok.decode(t, skip_from=self.ts_begin))
+            if self.align is not None:
+                # per text token the index of its segment in ``r.segments``
+                # (None: a segment dropped for its empty text)
+                seg_of, n = [], len(r.segments)
+                for sg in segs:
+                    kept = bool(self.tok.decode(sg.tokens, skip_from=self.ts_begin).strip())
+                    seg_of += [n if kept else None] * len(sg.tokens)
+                    n += kept
             r.segments += out
             r.win_texts.append(" ".join(t for _, _, t in out))
             if segs and segs[-1].open:
@@ -1142,6 +1189,9 @@ class STTEngine:
             r.prev_tokens = (r.prev_tokens + toks)[-max(PREV_TOKENS, 1):]
         if self.fallback and r.target is None and self.temperatures[r.attempt] > 0.5:
             r.prev_tokens = []      # Whisper's prompt reset: a hot window does not prompt the next
+        if self.align is not None and not gated:
+            # a kept window (not gated, not a discarded fallback attempt)
+            self._align_window(r, seg_of)
         if r.logprobs and not gated:
             # fp64 sum of the window's f32 values; -inf (nothing allowed) stays -inf
             r.lp_sum += float(np.sum(np.asarray(r.logprobs, np.float64)))
@@ -1166,6 +1216,57 @@ class STTEngine:
                 self.stats["logprob_sum"] += r.lp_sum
         self.stats["utterances"] += 1
         return r
+
+    def align_rows(self, r: STTRequest) -> tuple[list, list, int | None, int]:
+        """What the alignment of ``r``'s current window reads: (``rows``, the
+        indices into ``r.tokens`` of its text tokens, the index of a sampled EOT
+        or None, ``n_lead``). The row of sampled token k is the input position
+        whose logits produced it, ``prompt_len - 1 + k``; ``rows`` = the
+        positions of the SOT-sequence inputs but the last (``n_lead`` leading
+        rows: normalised over, then dropped), the text tokens' rows, the EOT's.
+        Rows that produced timestamp tokens and the previous-text prompt are
+        left out."""
+        ts_begin = self.ts_begin if self.timestamps else None
+        idx = [k for k, t in enumerate(r.tokens)
+               if t != self.eot and (ts_begin is None or t < ts_begin)]
+        eot_k = next((k for k, t in enumerate(r.tokens) if t == self.eot), None)
+        n_lead = len(self.sot) - 1
+        p0, base = r.prompt_len - len(self.sot), r.prompt_len - 1
+        rows = list(range(p0, p0 + n_lead)) + [base + k for k in idx]
+        if eot_k is not None:
+            rows.append(base + eot_k)
+        return rows, idx, eot_k, n_lead
+
+    def window_frames(self, r: STTRequest) -> int:
+        """20 ms frames of the audio in ``r``'s current window."""
+        return ops.ref.align_frames(min(N_SAMPLES, r.n_samples - r.win * N_SAMPLES),
+                                    self.cfg.n_audio_ctx)
+
+    def _align_window(self, r: STTRequest, seg_of: list | None) -> None:
+        """Word timestamps of ``r``'s kept window: three launches on this
+        stream (scores, cost, DTW) over the queries its steps recorded, one
+        synchronous read-back of ``tok_frame``, then the host's word assembly.
+        Writes to the query store go by (slot, position) and are stream-ordered
+        before this: a fallback retry, a discarded speculative step or a reused
+        slot only touched positions outside ``rows`` or rewrote them since."""
+        rows, idx, eot_k, n_lead = self.align_rows(r)
+        if not idx:
+            r.token_frames.append([])
+            return
+        F = self.window_frames(r)
+        frames = self.align.align(r.slot, rows, self.xkv, F, n_lead)
+        r.token_frames.append(frames)
+        lps = [r.logprobs[k] for k in idx] \
+            if r.target is None and len(r.logprobs) == len(r.tokens) else None
+        if seg_of is None:
+            seg_of = [r.win] * len(idx)
+        words = window_words(self.tok.decode, [r.tokens[k] for k in idx], frames[: len(idx)],
+                             frames[len(idx)] if eot_k is not None else F, lps,
+                             r.language or self.language, seg_of)
+        r.words += utterance_words(words, r.win, r.n_samples / 16000.0)
+        r.word_segments += [w.segment for w in words]
+        self.stats["aligned_windows"] += 1
+        self.stats["aligned_words"] += len(words)
 
     def transcribe(self, reqs: list[STTRequest], device_pcm: torch.Tensor | None = None
                    ) -> list[STTRequest]:

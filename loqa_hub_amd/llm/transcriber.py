@@ -44,6 +44,12 @@ class TranscriptionResult:
     # of the windows' texts
     temperature: float | None = None
     compression_ratio: float | None = None
+    # HUB_STT_WORD_TIMESTAMPS=on (gpu backend; else None): (start_s, end_s, word,
+    # probability) in utterance time, the decoder's words before the wake-word
+    # cut, and the start of the first word after the wake word's words (None
+    # without a wake word or without a word after it)
+    words: list | None = None
+    command_start_s: float | None = None
 
 
 @dataclass
@@ -106,6 +112,17 @@ def post_process_transcription(raw: str) -> PostProcessingResult:
     return res
 
 
+def command_start(words, wake_word_variant: str) -> float | None:
+    """``post_process_transcription``'s wake-word cut in seconds: the start of
+    the first word after the wake word's words (``len(variant.split())`` of
+    ``words``, (start_s, end_s, word, probability) tuples); None without a wake
+    word or without a word after it."""
+    if not words or not wake_word_variant:
+        return None
+    n = len(wake_word_variant.split())
+    return float(words[n][0]) if n < len(words) else None
+
+
 def to_transcription_result(raw: str, avg_logprob: float | None = None,
                             confirm_below: float = CONFIRMATION_THRESHOLD, *,
                             language: str | None = None, language_prob: float | None = None,
@@ -113,7 +130,8 @@ def to_transcription_result(raw: str, avg_logprob: float | None = None,
                             speech_start_s: float | None = None,
                             speech_end_s: float | None = None,
                             temperature: float | None = None,
-                            compression_ratio: float | None = None) -> TranscriptionResult:
+                            compression_ratio: float | None = None,
+                            words: list | None = None) -> TranscriptionResult:
     """``avg_logprob`` (the on-device Whisper decode's mean token
     log-probability): the confidence is the geometric-mean token probability
     ``min(1, exp(avg_logprob))`` instead of the text heuristic, and a
@@ -123,11 +141,15 @@ def to_transcription_result(raw: str, avg_logprob: float | None = None,
     at the start-of-transcript position, carried as they are; so are
     ``segments`` / ``speech_start_s`` / ``speech_end_s`` of a decode with
     timestamps (their texts are the decoder's, before the wake-word cut), and
-    ``temperature`` / ``compression_ratio`` of a decode with temperature fallback."""
+    ``temperature`` / ``compression_ratio`` of a decode with temperature fallback,
+    and ``words`` of a decode with word timestamps, from which ``command_start_s``
+    (the wake-word cut in seconds) is read."""
     p = post_process_transcription(raw)
     probe = dict(language=language, language_prob=language_prob, no_speech_prob=no_speech_prob,
                  segments=segments, speech_start_s=speech_start_s, speech_end_s=speech_end_s,
-                 temperature=temperature, compression_ratio=compression_ratio)
+                 temperature=temperature, compression_ratio=compression_ratio, words=words,
+                 command_start_s=command_start(words, p.wake_word_variant)
+                 if p.wake_word_detected else None)
     if avg_logprob is None:
         return TranscriptionResult(p.cleaned_text, p.confidence_estimate, p.wake_word_detected,
                                    p.wake_word_variant, p.needs_confirmation, **probe)

@@ -281,9 +281,13 @@ class WhisperModel:
                     cu_q: torch.Tensor, ctx_lens: torch.Tensor, block_tables: torch.Tensor,
                     max_q: int, max_ctx: int, k_cache: torch.Tensor, v_cache: torch.Tensor,
                     xkv: list[torch.Tensor], enc_starts: torch.Tensor, enc_lens: torch.Tensor,
-                    logit_idx: torch.Tensor, ws: ops.AttnWorkspace | None) -> torch.Tensor:
+                    logit_idx: torch.Tensor, ws: ops.AttnWorkspace | None,
+                    align: tuple | None = None) -> torch.Tensor:
         """One decoder forward over a flat token batch; returns logits [B, V] of
-        ``logit_idx`` rows. Self-attn K/V go to the paged cache (no RoPE)."""
+        ``logit_idx`` rows. Self-attn K/V go to the paged cache (no RoPE).
+        ``align`` = (``ops.AlignStore``, the step's ``row_slot``): the step ends
+        with one ``ops.align_record`` launch that keeps the alignment heads'
+        cross-attention queries (word timestamps)."""
         cfg, w = self.cfg, self.w
         d, H, D = cfg.d_model, cfg.n_heads, cfg.head_dim
         x = torch.nn.functional.embedding(tokens.long(), w.tok_embed)
@@ -294,6 +298,7 @@ class WhisperModel:
         enc_splits = (cfg.n_audio_ctx + 255) // 256
         self_splits = max(1, (max_ctx + 255) // 256)
         grouped = max_q <= 128
+        qs = {}
         for i, L in enumerate(w.dec):
             if i > 0:
                 h = ops.layernorm(delta, L["ln1_w"], L["ln1_b"], 1e-5, residual=residual)
@@ -307,6 +312,8 @@ class WhisperModel:
             o = ops.linear(a, L["wo"], L["bo"])
             h = ops.layernorm(o, L["lnx_w"], L["lnx_b"], 1e-5, residual=residual)
             q = ops.linear(h, L["xq"], L["xq_b"])
+            if align is not None and i in align[0].layers:
+                qs[i] = q
             kv = xkv[i]
             xa = ops.attention(q, kv, kv[:, d:], cu_q, n_heads=H, n_kv=H, head_dim=D, causal=False,
                                max_q=max_q, cu_k=enc_starts, ctx_lens=enc_lens,
@@ -317,6 +324,8 @@ class WhisperModel:
             m = ops.linear(h, L["fc1"], L["fc1_b"])
             ops.gelu_bias_(m)
             delta = ops.linear(m, L["fc2"], L["fc2_b"])
+        if align is not None:
+            align[0].record(qs, positions, slots, cu_q, align[1])
         sel_r = residual.index_select(0, logit_idx).contiguous()
         sel_d = delta.index_select(0, logit_idx).contiguous()
         hf = ops.layernorm(sel_d, w.dec_ln_w, w.dec_ln_b, 1e-5, residual=sel_r)
@@ -328,21 +337,24 @@ def decode_step_fast(model: "WhisperModel", tokens: torch.Tensor, positions: tor
                      block_tables: torch.Tensor, max_q: int, k_cache: torch.Tensor,
                      v_cache: torch.Tensor, xkv: list[torch.Tensor], enc_starts: torch.Tensor,
                      enc_lens: torch.Tensor, logit_idx: torch.Tensor, ws,
-                     self_splits: int, split_keys: int = 128) -> torch.Tensor:
+                     self_splits: int, split_keys: int = 128,
+                     align: tuple | None = None) -> torch.Tensor:
     """Decoder step on the weight-streaming path: every projection is the
     skinny split-K MFMA GEMM whose f32 slabs are reduced by the fused consumer
     that follows (bias + residual + LayerNorm, bias + KV append, bias + GELU);
     self- and cross-attention use the split-key decode kernel (cross-attention
     reads the encoder K/V rows in place). ``tokens`` has Mpad rows (padding
     rows carry slot -1); ``logit_idx`` has >= 16 rows. Graph-capturable: no
-    host synchronisation, fixed ``self_splits``. Returns f32 logits
-    [len(logit_idx), vocab_pad]."""
+    host synchronisation, fixed ``self_splits``. ``align``: as
+    ``WhisperModel.decode_step`` (one more launch at the end of the step).
+    Returns f32 logits [len(logit_idx), vocab_pad]."""
     cfg, w = model.cfg, model.w
     d, H, D = cfg.d_model, cfg.n_heads, cfg.head_dim
     enc_splits = (cfg.n_audio_ctx + split_keys - 1) // split_keys
     residual = ops.embed_pos(tokens, positions, w.tok_embed, w.dec_pos)
     h = ops.layernorm(residual, w.dec[0]["ln1_w"], w.dec[0]["ln1_b"], 1e-5)
     part = None
+    qs = {}
     for i, (L, P) in enumerate(zip(w.dec, w.dec_p)):
         if i > 0:
             h = ops.slab_layernorm(part, residual, L["ln1_w"], L["ln1_b"], 1e-5,
@@ -358,6 +370,8 @@ def decode_step_fast(model: "WhisperModel", tokens: torch.Tensor, positions: tor
         h = ops.slab_layernorm(part, residual, L["lnx_w"], L["lnx_b"], 1e-5, bias=L["bo"])
         part = ops.skinny_gemm(h, P["xq"])
         q = ops.slab_bias_act(part, L["xq_b"])
+        if align is not None and i in align[0].layers:
+            qs[i] = q
         kv = xkv[i]
         a = ops.attention(q, kv, kv[:, d:], cu_q, n_heads=H, n_kv=H, head_dim=D, causal=False,
                           max_q=max_q, cu_k=enc_starts, ctx_lens=enc_lens, grouped=True,
@@ -367,6 +381,8 @@ def decode_step_fast(model: "WhisperModel", tokens: torch.Tensor, positions: tor
         part = ops.skinny_gemm(h, P["fc1"])
         m = ops.slab_bias_act(part, L["fc1_b"], "gelu")
         part = ops.skinny_gemm(m, P["fc2"])
+    if align is not None:
+        align[0].record(qs, positions, slots, cu_q, align[1])
     hf = ops.slab_layernorm(part, residual, w.dec_ln_w, w.dec_ln_b, 1e-5,
                             bias=w.dec[-1]["fc2_b"], row_idx=logit_idx, write_residual=False)
     return ops.skinny_gemm(hf, w.lm_head_p, 1, max_wgs=getattr(w, "max_wgs", ops.MAX_DECODE_WGS))[0]
@@ -378,7 +394,7 @@ def decode_step_fused(model: "WhisperModel", tokens: torch.Tensor, positions: to
                       v_cache: torch.Tensor, xkv: list[torch.Tensor], enc_starts: torch.Tensor,
                       enc_lens: torch.Tensor, logit_idx: torch.Tensor, ws, scratch,
                       self_splits: int, split_keys: int = 128,
-                      cross_split_keys: int = 512) -> torch.Tensor:
+                      cross_split_keys: int = 512, align: tuple | None = None) -> torch.Tensor:
     """Decoder step on the fused-epilogue GEMMs: 8 launches per layer.
 
     qkv   (LayerNorm ln1 prologue | bias + q / paged K,V append epilogue) ->
@@ -388,7 +404,9 @@ def decode_step_fused(model: "WhisperModel", tokens: torch.Tensor, positions: to
     fc2   (bias + residual + row stats).
     The LayerNorm statistics of a row come from the previous residual
     epilogue's per-tile partial sums, so no separate norm launch exists. Same
-    contract as ``decode_step_fast``; Mpad (tokens rows) 16 or 32."""
+    contract as ``decode_step_fast``; Mpad (tokens rows) 16 or 32. With ``align``
+    the xq GEMM of every alignment layer writes into that layer's own buffer
+    (``AlignStore.qbuf``) and the step ends with the record launch."""
     cfg, w = model.cfg, model.w
     d, H, D = cfg.d_model, cfg.n_heads, cfg.head_dim
     enc_splits = (cfg.n_audio_ctx + cross_split_keys - 1) // cross_split_keys
@@ -409,14 +427,17 @@ def decode_step_fused(model: "WhisperModel", tokens: torch.Tensor, positions: to
                                        num_splits=self_splits, workspace=ws))
         ops.skinny_fused(a, F["o"], "resid", scratch, residual=residual, row_sums=True)
         kv = xkv[i]
+        qo = align[0].qbuf[i][:Mpad] if align is not None and i in align[0].layers else None
         a = ops.skinny_fused(residual, F["xq"], "act", scratch, eps=1e-5, n_heads=H, n_kv=H,
-                             head_dim=D,
+                             head_dim=D, out=qo,
                              attn=dict(cu_q=cu_q, ctx_lens=enc_lens, kv_start=enc_starts, k=kv,
                                        v=kv[:, d:], max_q=max_q, split_keys=cross_split_keys,
                                        num_splits=enc_splits, workspace=ws))
         ops.skinny_fused(a, F["xo"], "resid", scratch, residual=residual, row_sums=True)
         m = ops.skinny_fused(residual, F["fc1"], "act", scratch, act="gelu", eps=1e-5)
         ops.skinny_fused(m, F["fc2"], "resid", scratch, residual=residual, row_sums=True)
+    if align is not None:
+        align[0].record(align[0].qbuf, positions, slots, cu_q, align[1])
     if ops.FUSED_EMBED:
         hf = ops.layernorm(residual, w.dec_ln_w, w.dec_ln_b, 1e-5, row_idx=logit_idx)
     else:

@@ -479,6 +479,233 @@ def gumbel_noise(rng: torch.Tensor, V: int) -> torch.Tensor:
     return out
 
 
+# -------------------------------------------- word timestamps (alignment)
+def _i32(t: torch.Tensor, name: str, device) -> None:
+    if t.dtype != torch.int32 or not t.is_contiguous() or t.device != device:
+        raise ValueError(f"{name}: a contiguous int32 tensor on {device}")
+
+
+def _align_heads(heads, n_layers_given, H: int) -> list:
+    heads = [(int(l), int(h)) for l, h in heads]
+    if not 1 <= len(heads) <= ref.MAX_ALIGN_HEADS:
+        raise ValueError(f"{len(heads)} alignment heads: 1 .. {ref.MAX_ALIGN_HEADS}")
+    for l, h in heads:
+        if l not in n_layers_given or not 0 <= h < H:
+            raise ValueError(f"alignment head {l}:{h}: no such layer buffer / head")
+    return heads
+
+
+def align_record(qs: dict, heads, positions: torch.Tensor, slots: torch.Tensor,
+                 cu_q: torch.Tensor, row_slot: torch.Tensor, align_q: torch.Tensor) -> None:
+    """Keep a decoder step's cross-attention queries of the alignment heads:
+    row r with ``slots[r] >= 0`` copies head (l, h)'s D values of ``qs[l]``
+    ([rows, H * D] bf16, the layer's xq output) to ``align_q[row_slot[b], a,
+    positions[r]]`` (``align_q`` [slots, A, n_text_ctx, D] bf16), b the sequence
+    with ``cu_q[b] <= r < cu_q[b + 1]``. One launch, 16-byte copies, padding rows
+    write nothing; a slot or position outside ``align_q`` writes nothing."""
+    if align_q.dim() != 4 or align_q.dtype != torch.bfloat16 or not align_q.is_contiguous():
+        raise ValueError("align_q: contiguous bf16 [slots, A, n_text_ctx, D]")
+    S, A, n_ctx, D = align_q.shape
+    dev = align_q.device
+    T = slots.numel()
+    for name, t in (("positions", positions), ("slots", slots), ("cu_q", cu_q),
+                    ("row_slot", row_slot)):
+        _i32(t, name, dev)
+    B = cu_q.numel() - 1
+    if positions.numel() < T or B < 1 or row_slot.numel() < B:
+        raise ValueError("align_record: positions / cu_q / row_slot do not cover the step")
+    ld = {int(q.stride(0)) for q in qs.values()}
+    if len(ld) != 1:
+        raise ValueError("align_record: the layers' query buffers differ in row stride")
+    ldq = ld.pop()
+    H = min(q.shape[1] for q in qs.values()) // D
+    heads = _align_heads(heads, qs, H)
+    if len(heads) != A:
+        raise ValueError(f"align_record: {len(heads)} heads, align_q holds {A}")
+    for q in qs.values():
+        if q.dtype != torch.bfloat16 or q.stride(1) != 1 or q.shape[0] < T or q.device != dev:
+            raise ValueError("align_record: query buffers are bf16 [>= rows, H * D] on the device")
+    if D % 8 or ldq % 8:
+        raise ValueError("align_record: D and the row stride must be multiples of 8")
+    if not _gpu(align_q):
+        return ref.align_record(qs, heads, positions, slots, cu_q, row_slot, align_q)
+    ptrs = (ctypes.c_void_p * A)(*[qs[l].data_ptr() + h * D * 2 for l, h in heads])
+    check(kernels().loqa_align_record(ptrs, A, D, ldq, ptr(positions), ptr(slots), ptr(cu_q),
+                                      ptr(row_slot), T, B, ptr(align_q), S, n_ctx,
+                                      stream_ptr(align_q)), "align_record")
+
+
+def align_scores(aq: torch.Tensor, rows: torch.Tensor, xkv, heads, k_row0: int, F: int,
+                 scale: float | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Whisper's alignment weights of one window: ``aq`` [A, n_text_ctx, D] bf16
+    (one slot of the query store), ``rows`` int32 [R] (positions in it), ``xkv``
+    the layers' cross-attention K|V buffers (K of head h of layer l = columns
+    h * D .. of ``xkv[l]``, the window's encoder rows start at ``k_row0``) ->
+    P [A, R, F] f32, P[a, r, :] = softmax_f(scale * q . k) over the first ``F``
+    frames (``scale`` default 1 / sqrt(D)). bf16 MFMA, f32 softmax; K rows >= F
+    and positions outside ``rows`` are not read."""
+    if aq.dim() != 3 or aq.dtype != torch.bfloat16 or not aq.is_contiguous():
+        raise ValueError("aq: contiguous bf16 [A, n_text_ctx, D]")
+    A, n_ctx, D = aq.shape
+    dev = aq.device
+    _i32(rows, "rows", dev)
+    R = rows.numel()
+    xkv = dict(enumerate(xkv)) if not isinstance(xkv, dict) else xkv
+    heads = _align_heads(heads, xkv, min(k.shape[1] for k in xkv.values()) // D)
+    if len(heads) != A:
+        raise ValueError(f"align_scores: {len(heads)} heads, aq holds {A}")
+    ld = {int(xkv[l].stride(0)) for l, _ in heads}
+    if len(ld) != 1:
+        raise ValueError("align_scores: the layers' K|V buffers differ in row stride")
+    ldk = ld.pop()
+    for l, _ in heads:
+        k = xkv[l]
+        if k.dtype != torch.bfloat16 or k.stride(1) != 1 or k.device != dev or \
+                k_row0 < 0 or k_row0 + F > k.shape[0]:
+            raise ValueError("align_scores: K|V buffers are bf16 rows on the device holding "
+                             "rows k_row0 .. k_row0 + F")
+    if R < 1 or F < 1:
+        raise ValueError("align_scores: R and F must be >= 1")
+    if rows.device.type == "cpu" and (int(rows.min()) < 0 or int(rows.max()) >= n_ctx):
+        raise ValueError("align_scores: a row lies outside the query store")
+    if D not in (32, 64, 128) or ldk % 8:
+        raise ValueError("align_scores: head_dim 32, 64 or 128 and a row stride that is a "
+                         "multiple of 8")
+    scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
+    if not _gpu(aq):
+        q = aq[:, rows.long()]
+        k = torch.stack([xkv[l][k_row0:k_row0 + F, h * D:(h + 1) * D] for l, h in heads])
+        P = ref.align_scores(q, k, scale)
+        if out is not None:
+            out[: P.numel()].view(P.shape).copy_(P)
+        return P
+    if out is None:
+        out = torch.empty(A * R * F, dtype=torch.float32, device=dev)
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < A * R * F:
+        raise ValueError("align_scores: out holds fewer than A * R * F floats")
+    ptrs = (ctypes.c_void_p * A)(*[xkv[l].data_ptr() + (k_row0 * ldk + h * D) * 2
+                                   for l, h in heads])
+    check(kernels().loqa_align_scores(ptr(aq), ptr(rows), R, ptrs, A, D, n_ctx, ldk, F, scale,
+                                      ptr(out), stream_ptr(aq)), "align_scores")
+    return out.view(-1)[: A * R * F].view(A, R, F)
+
+
+def align_cost(P: torch.Tensor, n_lead: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """``ref.align_cost``: P [A, R, F] f32 -> the DTW cost [R - n_lead, F] f32
+    (rows normalised per head and frame, median filter of width 7 over the
+    frames, mean over the heads, negated). Every sum runs in a fixed order:
+    repeated launches agree bitwise."""
+    if P.dim() != 3 or P.dtype != torch.float32 or not P.is_contiguous():
+        raise ValueError("P: contiguous f32 [A, R, F]")
+    A, R, F = P.shape
+    if not (1 <= A <= ref.MAX_ALIGN_HEADS and 0 <= n_lead < R and F >= 1):
+        raise ValueError(f"align_cost: A={A} R={R} F={F} n_lead={n_lead}")
+    N = R - n_lead
+    if not _gpu(P):
+        c = ref.align_cost(P, n_lead)
+        if out is not None:
+            out.view(-1)[: c.numel()].view(c.shape).copy_(c)
+        return c
+    if out is None:
+        out = torch.empty(N * F, dtype=torch.float32, device=P.device)
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < N * F:
+        raise ValueError("align_cost: out holds fewer than N * F floats")
+    check(kernels().loqa_align_cost(ptr(P), A, R, F, n_lead, ptr(out), stream_ptr(P)),
+          "align_cost")
+    return out.view(-1)[: N * F].view(N, F)
+
+
+DTW_MAX_ROWS = 448
+
+
+def dtw_workspace(N: int, M: int) -> int:
+    """Bytes of trace workspace ``dtw`` needs for an N x M cost."""
+    return (N + M - 1) * N
+
+
+def dtw(x: torch.Tensor, trace: torch.Tensor | None = None,
+        tok_frame: torch.Tensor | None = None, total: torch.Tensor | None = None
+        ) -> tuple[torch.Tensor, torch.Tensor]:
+    """``ref.dtw`` of the cost x [N, M] f32, N <= 448: (tok_frame int32 [N], the
+    frame of the first path cell of every row; the total cost f32 [1]), both on
+    x's device and bit for bit the reference's. One workgroup walks the
+    anti-diagonal wavefront and the path back; ``trace`` (uint8,
+    ``dtw_workspace(N, M)`` bytes) holds the trace codes of a large cost."""
+    if x.dim() != 2 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError("dtw: x is a contiguous f32 [N, M]")
+    N, M = x.shape
+    if not (1 <= N <= DTW_MAX_ROWS and M >= 1):
+        raise ValueError(f"dtw: N={N} (1 .. {DTW_MAX_ROWS}), M={M} (>= 1)")
+    if not _gpu(x):
+        tf, c = ref.dtw(x, return_cost=True)
+        return torch.from_numpy(tf), torch.tensor([c], dtype=torch.float32)
+    need = dtw_workspace(N, M)
+    if trace is None:
+        trace = torch.empty(need, dtype=torch.uint8, device=x.device)
+    if trace.dtype != torch.uint8 or not trace.is_contiguous() or trace.numel() < need or \
+            trace.device != x.device:
+        raise ValueError(f"dtw: trace holds fewer than {need} bytes")
+    if tok_frame is None:
+        tok_frame = torch.empty(N, dtype=torch.int32, device=x.device)
+    if total is None:
+        total = torch.empty(1, dtype=torch.float32, device=x.device)
+    _i32(tok_frame, "tok_frame", x.device)
+    if tok_frame.numel() < N or total.dtype != torch.float32 or total.device != x.device:
+        raise ValueError("dtw: tok_frame holds fewer than N entries / total is not f32")
+    check(kernels().loqa_dtw(ptr(x), N, M, ptr(trace), ptr(tok_frame), ptr(total), stream_ptr(x)),
+          "dtw")
+    return tok_frame[:N], total
+
+
+class AlignStore:
+    """What an engine keeps for word timestamps: the alignment heads, the
+    per-slot query store ``align_q`` [slots, A, n_text_ctx, D] bf16 the decoder
+    steps record into, the alignment layers' query buffers of the fused step
+    (``qbuf[layer]`` [rows, H * D]) and one window's P / cost / trace workspaces.
+    Everything that writes or reads them runs on the engine's one stream."""
+
+    def __init__(self, cfg, heads, n_slots: int, device, max_rows: int = 128):
+        self.heads = [(int(l), int(h)) for l, h in heads]
+        self.layers = sorted({l for l, _ in self.heads})
+        A, D, H = len(self.heads), cfg.head_dim, cfg.n_heads
+        self.n_text_ctx, self.n_audio_ctx = cfg.n_text_ctx, cfg.n_audio_ctx
+        z = lambda *s, dt=torch.bfloat16: torch.zeros(*s, dtype=dt, device=device)  # noqa: E731
+        self.align_q = z(n_slots, A, cfg.n_text_ctx, D)
+        self.qbuf = {l: z(max_rows, H * D) for l in self.layers}
+        self.P = z(A * cfg.n_text_ctx * cfg.n_audio_ctx, dt=torch.float32)
+        self.cost = z(cfg.n_text_ctx * cfg.n_audio_ctx, dt=torch.float32)
+        self.trace = z(dtw_workspace(min(cfg.n_text_ctx, DTW_MAX_ROWS), cfg.n_audio_ctx),
+                       dt=torch.uint8)
+        self.tok_frame = z(cfg.n_text_ctx, dt=torch.int32)
+        self.total = z(1, dt=torch.float32)
+        self.host = torch.zeros(cfg.n_text_ctx, dtype=torch.int32)
+        if torch.device(device).type == "cuda":
+            self.host = self.host.pin_memory()
+
+    def record(self, qs: dict, positions, slots, cu_q, row_slot) -> None:
+        align_record({l: qs[l] for l in self.layers}, self.heads, positions, slots, cu_q, row_slot,
+                     self.align_q)
+
+    def align(self, slot: int, rows: list, xkv, F: int, n_lead: int) -> list:
+        """``tok_frame`` (a list of ints) of one window: the three alignment
+        launches on the current stream, the result copied to pinned memory and
+        waited for."""
+        dev = self.align_q.device
+        r = torch.tensor(rows, dtype=torch.int32)
+        if dev.type == "cuda":
+            r = r.pin_memory().to(dev, non_blocking=True)
+        P = align_scores(self.align_q[slot], r, xkv, self.heads, slot * self.n_audio_ctx, F,
+                         out=self.P)
+        cost = align_cost(P, n_lead, out=self.cost)
+        tf, _ = dtw(cost, self.trace, self.tok_frame, self.total)
+        n = len(rows) - n_lead
+        if dev.type != "cuda":
+            return [int(v) for v in tf[:n]]
+        self.host[:n].copy_(tf[:n], non_blocking=True)
+        torch.cuda.current_stream(dev).synchronize()
+        return [int(v) for v in self.host[:n]]
+
+
 # -------------------------------------------------------------------- audio
 def pcm16_to_f32_sumsq(pcm: torch.Tensor, offsets: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     """pcm: int16 [N] (concatenated segments), offsets: int64 [S+1].

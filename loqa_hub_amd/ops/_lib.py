@@ -182,6 +182,16 @@ _KERNEL_SIGS = {
                                   c_void_p],
     # (rng, B, V, out, stream)
     "loqa_gumbel_noise": [c_void_p, c_int, c_int, c_void_p, c_void_p],
+    # (q_ptrs[A], A, D, ldq, positions, slots, cu_q, row_slot, T, B, align_q, n_slots, n_ctx, stream)
+    "loqa_align_record": [c_void_p, c_int, c_int, c_ll, c_void_p, c_void_p, c_void_p, c_void_p,
+                          c_int, c_int, c_void_p, c_int, c_int, c_void_p],
+    # (align_q slot, rows, R, k_ptrs[A], A, D, n_ctx, ldk, F, scale, P, stream)
+    "loqa_align_scores": [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_ll, c_int,
+                          c_float, c_void_p, c_void_p],
+    # (P, A, R, F, n_lead, out, stream)
+    "loqa_align_cost": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
+    # (x, N, M, trace workspace, tok_frame, total, stream)
+    "loqa_dtw": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
 }
 
 # (argtypes, restype) of the custom all-reduce entry points (in the kernels library)

@@ -1088,3 +1088,164 @@ def whisper_decoder_ref(w, tokens: list[int], enc: torch.Tensor) -> torch.Tensor
         x = x + lin(gelu(lin(ln(x, L["ln2_w"], L["ln2_b"]), L["fc1"], L["fc1_b"])), L["fc2"],
                     L["fc2_b"])
     return ln(x, w.dec_ln_w, w.dec_ln_b) @ w.tok_embed.float().t()
+
+
+# ------------------------------------------------- word timestamps (alignment)
+# Whisper's find_alignment, in this engine's terms: the cross-attention queries
+# of the alignment heads are kept while a window is decoded (align_record), the
+# window's rows are scored against the encoder K rows (align_scores), normalised
+# over the rows, median-filtered over the frames and averaged over the heads
+# (align_cost), and dynamic time warping over that cost gives every token the
+# 20 ms frame at which it starts (dtw).
+MAX_ALIGN_HEADS = 32
+ALIGN_MEDIAN_WIDTH = 7
+
+
+def alignment_heads(dec_layers: int, n_heads: int, spec: str | None = None,
+                    generation_config: dict | None = None) -> list:
+    """The alignment heads as a list of (layer, head). In order: ``spec``
+    (``HUB_STT_ALIGNMENT_HEADS``, "l:h,l:h,..."), the checkpoint's
+    ``generation_config["alignment_heads"]``, else every head of the upper half
+    of the decoder layers (Whisper's default). At most ``MAX_ALIGN_HEADS``: the
+    per-slot query store is A * n_text_ctx * D * 2 bytes."""
+    if spec is not None and str(spec).strip():
+        heads = []
+        for item in str(spec).split(","):
+            try:
+                l, h = item.strip().split(":")
+                heads.append((int(l), int(h)))
+            except ValueError:
+                raise ValueError(f"HUB_STT_ALIGNMENT_HEADS {spec!r}: expected 'layer:head,...'") \
+                    from None
+    elif generation_config and generation_config.get("alignment_heads"):
+        heads = [(int(l), int(h)) for l, h in generation_config["alignment_heads"]]
+    else:
+        heads = [(l, h) for l in range(dec_layers // 2, dec_layers) for h in range(n_heads)]
+    if not heads:
+        raise ValueError("HUB_STT_ALIGNMENT_HEADS: no alignment heads")
+    if len(heads) > MAX_ALIGN_HEADS:
+        raise ValueError(f"HUB_STT_ALIGNMENT_HEADS: {len(heads)} alignment heads, at most "
+                         f"{MAX_ALIGN_HEADS} (name them with HUB_STT_ALIGNMENT_HEADS)")
+    if len(set(heads)) != len(heads):
+        raise ValueError(f"HUB_STT_ALIGNMENT_HEADS: duplicate heads in {heads}")
+    for l, h in heads:
+        if not (0 <= l < dec_layers and 0 <= h < n_heads):
+            raise ValueError(f"HUB_STT_ALIGNMENT_HEADS: head {l}:{h} outside {dec_layers} layers "
+                             f"x {n_heads} heads")
+    return heads
+
+
+def align_frames(window_samples: int, n_audio_ctx: int) -> int:
+    """Frames (20 ms each) of a window's audio: min(n_audio_ctx, max(1, ceil(samples / 320)))."""
+    return min(n_audio_ctx, max(1, -(-int(window_samples) // 320)))
+
+
+def align_record(qs: dict, heads, positions, slots, cu_q, row_slot, align_q) -> None:
+    """Row r of a step (``slots[r] >= 0``) copies the D values of every
+    alignment head from its layer's query buffer ``qs[layer]`` [Mpad, H * D] to
+    ``align_q[row_slot[b], a, positions[r]]``, b the sequence with
+    ``cu_q[b] <= r < cu_q[b + 1]``. Padding rows write nothing."""
+    D = align_q.shape[-1]
+    cu = [int(c) for c in cu_q]
+    for r in range(len(slots)):
+        if int(slots[r]) < 0:
+            continue
+        b = next((b for b in range(len(cu) - 1) if cu[b] <= r < cu[b + 1]), None)
+        if b is None:
+            continue
+        s, p = int(row_slot[b]), int(positions[r])
+        if not (0 <= s < align_q.shape[0] and 0 <= p < align_q.shape[2]):
+            continue
+        for a, (l, h) in enumerate(heads):
+            align_q[s, a, p] = qs[l][r, h * D:(h + 1) * D]
+
+
+def align_scores(q, k, scale: float):
+    """q [A, R, D], k [A, F, D] -> P[a, r, :] = softmax_f(scale * q[a, r] . k[a, f]),
+    f32 (fp64 inputs: fp64)."""
+    dt = torch.float64 if q.dtype == torch.float64 else torch.float32
+    s = torch.einsum("ard,afd->arf", q.to(dt), k.to(dt)) * scale
+    return torch.softmax(s, dim=-1)
+
+
+def align_cost(P, n_lead: int):
+    """Whisper's alignment matrix from P [A, R, F]: per (a, f) normalise over
+    the R rows (population std; 0 where it is 0: a frame whose rows all hold
+    the same value, whatever the rounding of their mean), median filter of
+    width 7 along f with reflect padding (F <= 3: unchanged), mean over the
+    heads, negated, without the first ``n_lead`` rows -> [R - n_lead, F]."""
+    mean = P.mean(dim=1, keepdim=True)
+    std = (P - mean).pow(2).mean(dim=1, keepdim=True).sqrt()
+    std = torch.where((P == P[:, :1]).all(dim=1, keepdim=True), torch.zeros_like(std), std)
+    Z = torch.where(std == 0, torch.zeros_like(P), (P - mean) / torch.where(std == 0, 1, std))
+    pad = ALIGN_MEDIAN_WIDTH // 2
+    if Z.shape[-1] > pad:
+        Zp = torch.nn.functional.pad(Z, (pad, pad), mode="reflect")
+        Z = Zp.unfold(-1, ALIGN_MEDIAN_WIDTH, 1).sort(dim=-1)[0][..., pad]
+    return -(Z.sum(dim=0) / Z.shape[0])[n_lead:].contiguous()
+
+
+def _dtw_cells(x: np.ndarray):
+    """Whisper's recurrence, literally: column-major j, i in f32."""
+    N, M = x.shape
+    cost = np.full((N + 1, M + 1), np.inf, np.float32)
+    trace = np.full((N + 1, M + 1), -1, np.int8)
+    cost[0, 0] = 0
+    for j in range(1, M + 1):
+        for i in range(1, N + 1):
+            c0, c1, c2 = cost[i - 1, j - 1], cost[i - 1, j], cost[i, j - 1]
+            if c0 < c1 and c0 < c2:
+                c, t = c0, 0
+            elif c1 < c0 and c1 < c2:
+                c, t = c1, 1
+            else:
+                c, t = c2, 2
+            cost[i, j] = x[i - 1, j - 1] + c
+            trace[i, j] = t
+    return cost, trace
+
+
+def _dtw_wavefront(x: np.ndarray):
+    """The same cells, a whole anti-diagonal i + j = t at a time (the order the
+    device kernel takes): a cell reads only cells of the two diagonals before."""
+    N, M = x.shape
+    cost = np.full((N + 1, M + 1), np.inf, np.float32)
+    trace = np.full((N + 1, M + 1), -1, np.int8)
+    cost[0, 0] = 0
+    for t in range(2, N + M + 1):
+        i = np.arange(max(1, t - M), min(N, t - 1) + 1)
+        j = t - i
+        c0, c1, c2 = cost[i - 1, j - 1], cost[i - 1, j], cost[i, j - 1]
+        d = (c0 < c1) & (c0 < c2)
+        u = ~d & (c1 < c0) & (c1 < c2)
+        c = np.where(d, c0, np.where(u, c1, c2))
+        cost[i, j] = x[i - 1, j - 1] + c
+        trace[i, j] = np.where(d, 0, np.where(u, 1, 2))
+    return cost, trace
+
+
+def dtw(x, return_cost: bool = False, literal: bool = False):
+    """Dynamic time warping over the cost x [N, M] (f32), Whisper's recurrence
+    and backtrace: ``tok_frame[N]`` (int32), the frame of the first path cell
+    of every row (Whisper's ``jumps``); with ``return_cost`` also the total cost
+    c[N, M] (f32). ``literal``: the cell loop in Whisper's order (the wavefront
+    order computes the same f32 add of the same operands in every cell)."""
+    x = np.ascontiguousarray(x.detach().cpu().numpy() if torch.is_tensor(x) else x, np.float32)
+    N, M = x.shape
+    with np.errstate(invalid="ignore"):
+        cost, trace = (_dtw_cells if literal else _dtw_wavefront)(x)
+    trace[0, :] = 2
+    trace[:, 0] = 1
+    tok_frame = np.zeros(N, np.int32)
+    i, j = N, M
+    while i > 0 or j > 0:
+        if i > 0 and j > 0:
+            tok_frame[i - 1] = j - 1     # the last visit going back is the row's first cell
+        t = trace[i, j]
+        if t == 0:
+            i, j = i - 1, j - 1
+        elif t == 1:
+            i -= 1
+        else:
+            j -= 1
+    return (tok_frame, cost[N, M]) if return_cost else tok_frame

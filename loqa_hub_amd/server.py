@@ -120,7 +120,9 @@ def build_gpu_processor(cfg: Config, nats, device: str = "cuda:0", tts=None, *, 
                     timestamps=g.stt_timestamps == "segment",
                     max_initial_timestamp=g.stt_max_initial_timestamp,
                     temperatures=tuple(g.stt_temperature),
-                    compression_ratio_threshold=g.stt_compression_ratio_threshold)
+                    compression_ratio_threshold=g.stt_compression_ratio_threshold,
+                    word_timestamps=g.stt_word_timestamps == "on",
+                    alignment_heads=g.stt_alignment_heads or None)
     if llm is None:
         llm = LLMEngine(lcfg, device, seed=g.seed, max_seqs=g.max_batch, weights=lw,
                         max_seq_len=g.max_seq_len, block_size=g.kv_block, use_graphs=g.use_graphs,
