@@ -245,6 +245,10 @@ class GPUConfig:
     # generation config, else every head of the upper half of the decoder layers)
     stt_word_timestamps: str = "off"  # off | on
     stt_alignment_heads: str = ""
+    # beam search on the gpu backend (Whisper's BeamSearchDecoder, patience 1):
+    # hypotheses per freely decoded 30 s window, 1 = off (greedy). Not together
+    # with stt_timestamps, stt_word_timestamps or a temperature fallback list.
+    stt_beam_size: int = 1
     # relay audio: "fixed" (every chunk is 16 kHz, AudioChunk.sample_rate is
     # ignored: the reference's behaviour) or "relay" (the stream's own rate, one
     # of AUDIO_SAMPLE_RATES; the gpu STT resamples it to 16 kHz on the device,
@@ -420,6 +424,25 @@ class Config:
         if len(t) > 1 and self.gpu.stt_backend != "gpu":
             raise ConfigError("HUB_STT_TEMPERATURE with a fallback needs HUB_STT_BACKEND=gpu: "
                               f"{self.gpu.stt_backend}")
+        b = self.gpu.stt_beam_size
+        if not 1 <= b <= 8:
+            raise ConfigError(f"HUB_STT_BEAM_SIZE must be in 1..8: {b}")
+        if b > 1:
+            if self.gpu.stt_backend != "gpu":
+                raise ConfigError("HUB_STT_BEAM_SIZE > 1 needs HUB_STT_BACKEND=gpu: "
+                                  f"{self.gpu.stt_backend}")
+            if self.gpu.stt_timestamps == "segment":
+                raise ConfigError("HUB_STT_BEAM_SIZE > 1 does not combine with "
+                                  "HUB_STT_TIMESTAMPS=segment (beams carry no timestamp rule state)")
+            if self.gpu.stt_word_timestamps == "on":
+                raise ConfigError("HUB_STT_BEAM_SIZE > 1 does not combine with "
+                                  "HUB_STT_WORD_TIMESTAMPS=on (beams carry no query store)")
+            if len(t) > 1:
+                raise ConfigError("HUB_STT_BEAM_SIZE > 1 does not combine with a HUB_STT_TEMPERATURE "
+                                  f"fallback list: {t}")
+            if b > self.gpu.max_batch:
+                raise ConfigError(f"HUB_STT_BEAM_SIZE {b} exceeds HUB_MAX_BATCH "
+                                  f"{self.gpu.max_batch} (decoder rows)")
         if not self.gpu.stt_compression_ratio_threshold > 0.0:
             raise ConfigError("HUB_STT_COMPRESSION_RATIO_THRESHOLD must be > 0: "
                               f"{self.gpu.stt_compression_ratio_threshold}")
@@ -482,6 +505,17 @@ def _float_list(e, default: list, key: str) -> list:
         return [float(x) for x in v.split(",")]
     except ValueError:
         raise ConfigError(f"invalid configuration: invalid {key}: {v}") from None
+
+
+def _beam_size(e) -> int:
+    """HUB_STT_BEAM_SIZE: an integer (its range is checked in ``validate``);
+    empty / unset: 1, greedy decoding."""
+    v = env_str(e, "", "HUB_STT_BEAM_SIZE").strip()
+    if v == "":
+        return 1
+    if not re.fullmatch(r"[+-]?\d+", v):
+        raise ConfigError(f"invalid configuration: invalid HUB_STT_BEAM_SIZE: {v}")
+    return int(v)
 
 
 def load(env=None) -> Config:
@@ -572,6 +606,7 @@ def load(env=None) -> Config:
             stt_temperature=_float_list(e, [0.0], "HUB_STT_TEMPERATURE"),
             stt_word_timestamps=env_str(e, "off", "HUB_STT_WORD_TIMESTAMPS").strip().lower(),
             stt_alignment_heads="".join(env_str(e, "", "HUB_STT_ALIGNMENT_HEADS").split()),
+            stt_beam_size=_beam_size(e),
             stt_compression_ratio_threshold=_strict_float(e, 2.4,
                                                           "HUB_STT_COMPRESSION_RATIO_THRESHOLD"),
             audio_input_rate=env_str(e, "fixed", "HUB_AUDIO_INPUT_RATE").lower(),

@@ -149,6 +149,14 @@ class STTRequest:
     words: list | None = None
     word_segments: list | None = None
     token_frames: list = field(default_factory=list)
+    # STTEngine(beam_size=B > 1), free decoding: the beam width the request was
+    # decoded with (1: greedy, and every teacher-forced request), the last
+    # window's hypotheses as (tokens, sum_logprob), the winner (the highest
+    # sum_logprob / text tokens; it is ``tokens`` / ``logprobs``) first, and
+    # the same list for every window. A hypothesis that ended in EOT includes it.
+    beam_size: int = 1
+    hypotheses: list = field(default_factory=list)
+    window_hypotheses: list = field(default_factory=list)
     seq_id: int = -1
     t_done: float = 0.0
     t_enc0: float = 0.0               # encoder start / end, decoder start (perf_counter)
@@ -179,6 +187,11 @@ class STTRequest:
     lp_n: int = 0
     attempt: int = 0                  # index into the engine's temperatures (this window)
     prompt_len: int = 0               # tokens fed before the window's first sampled token
+    beam: object = None               # the window's BeamGroup while it is searched (stt_beam.py)
+    # debug: per beam the tokens its row is made to follow (parents forced to
+    # the identity), and per hypothesis the source row of each of its tokens
+    beam_force: list | None = None
+    hypothesis_traces: list = field(default_factory=list)
 
 
 class STTEngine:
@@ -202,8 +215,21 @@ class STTEngine:
                  no_speech_threshold: float = 0.6, logprob_threshold: float = -1.0,
                  timestamps: bool = False, max_initial_timestamp: float = 1.0,
                  temperatures=(0.0,), compression_ratio_threshold: float = 2.4,
-                 word_timestamps: bool = False, alignment_heads=None):
+                 word_timestamps: bool = False, alignment_heads=None, beam_size: int = 1):
         self.cfg = cfg
+        # beam search (engine/stt_beam.py): Whisper's BeamSearchDecoder with
+        # patience 1 over ``beam_size`` hypotheses per freely decoded window,
+        # selected on the device (ops.beam_topk / beam_merge), the KV moved
+        # between hypotheses by ops.kv_copy_blocks. 1: off, the greedy engine.
+        self.beam_size = int(beam_size)
+        if not 1 <= self.beam_size <= ops.BEAM_MAX:
+            raise ValueError(f"STT beam_size {beam_size} is outside 1..{ops.BEAM_MAX}")
+        if self.beam_size > 1 and (timestamps or word_timestamps or
+                                   len(check_temperatures(temperatures)) > 1):
+            raise ValueError("STT beam_size > 1 does not combine with timestamps, word "
+                             "timestamps or a temperature fallback schedule")
+        if self.beam_size > max_batch:
+            raise ValueError(f"STT beam_size {beam_size} exceeds max_batch {max_batch} (rows)")
         # temperature fallback (Whisper's decode_with_fallback): a freely decoded
         # window whose text is too repetitive (compression_ratio_threshold) or too
         # improbable (logprob_threshold) is decoded again at the next temperature,
@@ -242,7 +268,8 @@ class STTEngine:
         # timestamps ts_ctl) and a step returns three results
         self.row_fields = self.sot_probe or self.timestamps or self.fallback
         # (word timestamps report a probability per word: they record them too)
-        token_logprobs = bool(token_logprobs) or self.row_fields or bool(word_timestamps)
+        token_logprobs = bool(token_logprobs) or self.row_fields or bool(word_timestamps) or \
+            self.beam_size > 1
         self.token_logprobs = token_logprobs
         self.device = torch.device(device)
         if self.device.type == "cuda" and self.device.index is None:
@@ -340,6 +367,8 @@ class STTEngine:
             self.stats.update(timestamp_segments=0, open_segments=0)
         if self.fallback:
             self.stats.update(fallback_windows=0, fallback_attempts=0)
+        if self.beam_size > 1:
+            self.stats.update(beam_windows=0, beam_kv_copies=0)
         if self.timestamps:
             # the rule state of every cross-attention slot (+ a trash slot, the
             # last, for padding rows), beside ``last_tok``
@@ -406,6 +435,15 @@ class STTEngine:
         # two decoder steps in flight (the host prepares step j+1 while step j
         # runs); LOQA_STT_PIPELINE=0: one synchronous step at a time
         self.pipelined = self.use_graphs and os.environ.get("LOQA_STT_PIPELINE", "1") != "0"
+        # the beam engine: one synchronous eager-launch step at a time; a list
+        # in ``beam_debug`` collects every search step's beam_topk outputs
+        self._beam = None
+        self.beam_debug = None
+        if self.beam_size > 1:
+            from .stt_beam import BeamDecoder
+            self.pipelined = False
+            self.step_tokens = max(self.step_tokens, self.beam_size)
+            self._beam = BeamDecoder(self)
 
     def _init_probe(self, language: str, languages: list[str] | None) -> None:
         """Tokens of the start-of-transcript probe: ``nospeech`` and the
@@ -700,6 +738,8 @@ class STTEngine:
     def _argmax(self, logits: torch.Tensor):
         """Sampled tokens; with ``token_logprobs`` (tokens, their log-probabilities)."""
         fn = ops.masked_argmax_logprob if self.token_logprobs else ops.masked_argmax
+        if self._beam is not None:
+            self._beam.logits = logits
         if self._sup is None:
             return fn(logits)
         return fn(logits, self._sup, self._sup_rows[: logits.shape[0]])
@@ -710,6 +750,8 @@ class STTEngine:
         the step's ``probe`` field."""
         if not self.row_fields:
             return self._argmax(logits)
+        if self._beam is not None:
+            self._beam.logits = logits
         B = logits.shape[0]
         if self.fallback:
             # the rules (when on) plus a per-row temperature and random key: a
@@ -824,6 +866,8 @@ class STTEngine:
                 n += 1
         # a timestamps engine's prompt is one token shorter (a graph's max_q
         # follows it); its bucket set is that of the full prompt all the same
+        if self._beam is not None:      # beam steps launch eagerly: the encoder graphs alone
+            return n
         buckets = decode_buckets(self.SEQ_BUCKETS, self.max_batch, self.step_tokens,
                                  len(self.sot) + int(self.timestamps), self.SPLIT_KEYS,
                                  self.cfg.n_text_ctx)
@@ -845,7 +889,8 @@ class STTEngine:
             T_pad = ops.mpad_for(T)
             ctx = max(self.kv.pool.seq_len(r.seq_id) + len(r.feed) for r in live)
             C = min(self.cfg.n_text_ctx, -(-ctx // self.SPLIT_KEYS) * self.SPLIT_KEYS)
-            if self.use_graphs and ((B_pad, T_pad, C) in self._graphs or not self._graphs_frozen):
+            if self.use_graphs and self._beam is None and \
+                    ((B_pad, T_pad, C) in self._graphs or not self._graphs_frozen):
                 t0 = time.perf_counter()
                 g = self._graph(B_pad, T_pad, C)
                 hb = self.io.stage(g)
@@ -932,8 +977,14 @@ class STTEngine:
         return sum(n_windows(self._n_out(r), self.max_windows) for r in reqs)
 
     @property
+    def max_slots(self) -> int:
+        """Cross-attention slots in use at once: ``max_batch`` counts decoder
+        rows, and a searched window holds ``beam_size`` of them."""
+        return max(1, self.max_batch // self.beam_size)
+
+    @property
     def max_windows(self) -> int:
-        return max(1, min(MAX_WINDOWS, self.max_batch))
+        return max(1, min(MAX_WINDOWS, self.max_slots))
 
     def _encode(self, reqs: list[STTRequest], slots: list[int],
                 device_pcm: torch.Tensor | None = None) -> None:
@@ -981,6 +1032,8 @@ class STTEngine:
             r.attempt, r.fallback_attempts = 0, 0
             r.temperatures, r.compression_ratios = [], []
             r.token_frames = []
+            r.hypotheses, r.window_hypotheses, r.hypothesis_traces = [], [], []
+            r.beam_size = self.beam_size if self._window_text(r, 0) is None else 1
             r.words, r.word_segments = ([], []) if self.align is not None else (None, None)
             if self.fallback and r.sample_seed is None:
                 # a per-engine counter mixed with the engine seed
@@ -1009,6 +1062,7 @@ class STTEngine:
         rows; later windows are prompted with the previous windows' text."""
         r.win = w
         r.slot = r.slots[w]
+        r.beam = None
         r.seq_id = self._next
         self._next += 1
         self.kv.pool.add_seq(r.seq_id, [])
@@ -1072,6 +1126,8 @@ class STTEngine:
         """One decoder step over ``live`` (at most ``step_tokens`` tokens: a
         sequence may sit the step out or feed only part of its SOT prompt, see
         ``batching.plan_step``); returns the requests that finished."""
+        if self._beam is not None:
+            return self._beam.decode_once(live)
         take = plan_step([len(r.feed) for r in live], self.step_tokens, len(self.sot), self._rr)
         self._rr = (self._rr + self.step_tokens) % len(live) if len(live) > self.step_tokens else 0
         step, rest = [], []
@@ -1274,7 +1330,7 @@ class STTEngine:
         if not reqs:
             return reqs
         rows = self.rows_needed(reqs)
-        assert rows <= self.max_batch, "batch (30 s windows) exceeds max_batch"
+        assert rows <= self.max_slots, "batch (30 s windows) exceeds max_batch"
         self._admit(reqs, list(range(rows)), device_pcm)
         t_dec = time.monotonic()
         live, steps = list(reqs), 0
@@ -1297,7 +1353,7 @@ class STTEngine:
         tune_switch_interval()
         self._inbox: queue.Queue = queue.Queue()
         self._running = True
-        self._free_slots = list(range(self.max_batch))
+        self._free_slots = list(range(self.max_slots))
         self._sched = threading.Thread(target=self._schedule, args=(stream_priority,),
                                        name="stt-scheduler", daemon=True)
         self._sched.start()
@@ -1319,13 +1375,13 @@ class STTEngine:
             fut.set_exception(self._fatal)
             return fut
         reqs = list(reqs)
-        if len(reqs) > 1 and self.rows_needed(reqs) > self.max_batch:
+        if len(reqs) > 1 and self.rows_needed(reqs) > self.max_slots:
             # admission needs a free slot for every window of an inbox item: an
             # oversize batch would wait forever, so it goes in smaller items
             return join_futures([self.submit_batch([r], on_done) for r in reqs], reqs)
-        if self.rows_needed(reqs) > self.max_batch:
+        if self.rows_needed(reqs) > self.max_slots:
             fut.set_exception(ValueError(f"utterance needs {self.rows_needed(reqs)} 30 s windows "
-                                         f"> max_batch {self.max_batch}"))
+                                         f"> max_batch {self.max_slots}"))
             return fut
         self._inbox.put((reqs, on_done, fut))
         return fut
@@ -1458,12 +1514,14 @@ class STTEngine:
                     if not cell[1].done():
                         cell[1].set_exception(e)
                 for r in live:
+                    if self._beam is not None:
+                        self._beam.abort(r)
                     self.kv.pool.free_seq(r.seq_id)
                 for _, _, fut in waiting:
                     if not fut.done():
                         fut.set_exception(e)
                 live, waiting, cells, encoding = [], [], {}, []
-                self._free_slots = list(range(self.max_batch))
+                self._free_slots = list(range(self.max_slots))
 
     def _encoder_executor(self) -> ThreadPoolExecutor:
         if getattr(self, "_enc_pool", None) is None:

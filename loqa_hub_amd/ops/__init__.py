@@ -479,6 +479,115 @@ def gumbel_noise(rng: torch.Tensor, V: int) -> torch.Tensor:
     return out
 
 
+# --------------------------------------------------------------- beam search
+BEAM_MAX = 8        # widest beam of the kernels (csrc/kernels/beam.hip)
+
+
+def beam_topk(logits: torch.Tensor, mask: torch.Tensor | None, mask_rows: torch.Tensor | None,
+              eot: int, KB: int) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Per logits row the ``KB`` (<= 8) best allowed columns other than ``eot``
+    and their log-softmax after the mask, plus EOT's: (``cand_id`` int32
+    [R, KB], descending, ties to the lower column, -1 past the allowed count;
+    ``cand_lp`` float32 [R, KB]; ``eot_lp`` float32 [R], -inf when masked).
+    The sums run over every allowed column, EOT included, in
+    ``masked_argmax_logprob``'s order: ``cand_lp[r, 0]`` has that op's bits
+    whenever its winner is not EOT. Chunked like it (no memset, no atomics)."""
+    if logits.dim() != 2 or logits.stride(-1) != 1:
+        raise ValueError("beam_topk: logits must be [R, V] with unit column stride")
+    if logits.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError(f"beam_topk: logits must be bfloat16 or float32, got {logits.dtype}")
+    R, V = logits.shape
+    if not 1 <= int(KB) <= BEAM_MAX:
+        raise ValueError(f"beam_topk: KB {KB} is outside 1..{BEAM_MAX}")
+    if mask is not None:
+        _i32(mask, "beam_topk mask", logits.device)
+        if mask.dim() != 2 or mask.shape[-1] * 32 < V:
+            raise ValueError("beam_topk: mask must be [rows, >= ceil(V / 32)] packed words")
+        if mask_rows is not None:
+            _i32(mask_rows, "beam_topk mask_rows", logits.device)
+            if mask_rows.numel() != R:
+                raise ValueError("beam_topk: one mask row index per logits row")
+        elif mask.shape[0] < R:
+            raise ValueError("beam_topk: fewer mask rows than logits rows")
+    if not _gpu(logits):
+        return ref.beam_topk(logits, mask, mask_rows, int(eot), int(KB))
+    dev = logits.device
+    cand_id = torch.empty(R, KB, dtype=torch.int32, device=dev)
+    cand_lp = torch.empty(R, KB, dtype=torch.float32, device=dev)
+    eot_lp = torch.empty(R, dtype=torch.float32, device=dev)
+    chunks = (V + ARG_CHUNK - 1) // ARG_CHUNK
+    ws = None
+    if chunks > 1:
+        words = kernels().loqa_beam_topk_record_size() // 8
+        ws = torch.empty(R * chunks * words, dtype=torch.int64, device=dev)
+    check(kernels().loqa_beam_topk(
+        ptr(logits), int(logits.dtype == torch.bfloat16), logits.stride(0), R, V, ptr(mask),
+        ptr(mask_rows) if mask is not None else None, mask.shape[-1] if mask is not None else 0,
+        int(eot), int(KB), ptr(cand_id), ptr(cand_lp), ptr(eot_lp), ptr(ws), stream_ptr(logits)),
+        "beam_topk")
+    return cand_id, cand_lp, eot_lp
+
+
+def beam_merge(cand_id: torch.Tensor, cand_lp: torch.Tensor, eot_lp: torch.Tensor,
+               cum_in: torch.Tensor, n_src: int):
+    """The cross-beam selection of one step, per group g of ``cum_in`` [G, B]
+    (2 <= B <= 8): the B best of the ``n_src * B`` candidates of ``beam_topk``
+    rows ``g * n_src ..`` (``n_src`` 1 or B) by ``cum_in[g, src] + cand_lp``
+    (one f32 add), ranked score first, then the lower source beam, then the
+    lower column. Returns (tok, parent, lp, cum_out, eot_score, eot_fin), each
+    [G, B] (int32, int32, f32, f32, f32, int32); see ``ref.beam_merge``."""
+    if cum_in.dim() != 2 or cum_in.dtype != torch.float32 or not cum_in.is_contiguous():
+        raise ValueError("beam_merge: cum_in must be contiguous float32 [G, B]")
+    G, B = cum_in.shape
+    dev = cum_in.device
+    if not 2 <= B <= BEAM_MAX:
+        raise ValueError(f"beam_merge: B {B} is outside 2..{BEAM_MAX}")
+    if n_src not in (1, B):
+        raise ValueError(f"beam_merge: n_src {n_src} must be 1 or B = {B}")
+    _i32(cand_id, "beam_merge cand_id", dev)
+    for t, name, shape in ((cand_id, "cand_id", (G * n_src, B)), (cand_lp, "cand_lp", (G * n_src, B)),
+                           (eot_lp, "eot_lp", (G * n_src,))):
+        if tuple(t.shape) != shape or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"beam_merge: {name} must be contiguous {shape} on {dev}")
+    if cand_lp.dtype != torch.float32 or eot_lp.dtype != torch.float32:
+        raise TypeError("beam_merge: cand_lp and eot_lp must be float32")
+    if not _gpu(cum_in):
+        return ref.beam_merge(cand_id, cand_lp, eot_lp, cum_in, n_src)
+    i = lambda: torch.empty(G, B, dtype=torch.int32, device=dev)
+    f = lambda: torch.empty(G, B, dtype=torch.float32, device=dev)
+    tok, parent, lp, cum_out, eot_score, eot_fin = i(), i(), f(), f(), f(), i()
+    check(kernels().loqa_beam_merge(ptr(cand_id), ptr(cand_lp), ptr(eot_lp), ptr(cum_in), G, n_src,
+                                    B, ptr(tok), ptr(parent), ptr(lp), ptr(cum_out),
+                                    ptr(eot_score), ptr(eot_fin), stream_ptr(cum_in)), "beam_merge")
+    return tok, parent, lp, cum_out, eot_score, eot_fin
+
+
+def kv_copy_blocks(k: torch.Tensor, v: torch.Tensor, pairs) -> None:
+    """Copy paged KV blocks in place: for every (source block, destination
+    block) of ``pairs`` (a host list or array [P, 2]) and every layer,
+    ``k[:, dst] = k[:, src]`` and the same for ``v`` ([L, blocks, n_kv,
+    block_size, D], as ``PagedKVCache``), one launch. No block may be both a
+    source and a destination and no destination may repeat: a bad list raises
+    ValueError before anything is launched."""
+    if k.dim() != 5 or k.shape != v.shape or k.dtype != v.dtype or k.device != v.device:
+        raise ValueError("kv_copy_blocks: k and v must be equal [L, blocks, n_kv, block, D] caches")
+    if not (k.is_contiguous() and v.is_contiguous()):
+        raise ValueError("kv_copy_blocks: k and v must be contiguous")
+    if isinstance(pairs, torch.Tensor):
+        pairs = pairs.cpu().numpy()
+    p = ref.check_copy_pairs(pairs, k.shape[1])
+    if not len(p):
+        return
+    if not _gpu(k):
+        return ref.kv_copy_blocks(k, v, p)
+    block_bytes = k[0, 0].numel() * k.element_size()
+    if block_bytes % 16:
+        raise ValueError(f"kv_copy_blocks: a block of {block_bytes} bytes is not 16-byte vectors")
+    pd = torch.from_numpy(p).to(k.device)
+    check(kernels().loqa_kv_copy_blocks(ptr(k), ptr(v), k.shape[0], k.shape[1], block_bytes,
+                                        ptr(pd), len(p), stream_ptr(k)), "kv_copy_blocks")
+
+
 # -------------------------------------------- word timestamps (alignment)
 def _i32(t: torch.Tensor, name: str, device) -> None:
     if t.dtype != torch.int32 or not t.is_contiguous() or t.device != device:

@@ -192,6 +192,17 @@ _KERNEL_SIGS = {
     "loqa_align_cost": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     # (x, N, M, trace workspace, tok_frame, total, stream)
     "loqa_dtw": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    # (logits, is_bf16, ld, R, V, mask, mask_rows, W, eot, KB, cand_id, cand_lp, eot_lp,
+    #  workspace, stream)
+    "loqa_beam_topk": [c_void_p, c_int, c_ll, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
+                       c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "loqa_beam_topk_record_size": [],
+    # (cand_id, cand_lp, eot_lp, cum_in, G, n_src, B, tok, parent, lp, cum_out, eot_score,
+    #  eot_fin, stream)
+    "loqa_beam_merge": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    # (k, v, L, blocks, block_bytes, pairs, P, stream)
+    "loqa_kv_copy_blocks": [c_void_p, c_void_p, c_int, c_ll, c_ll, c_void_p, c_int, c_void_p],
 }
 
 # (argtypes, restype) of the custom all-reduce entry points (in the kernels library)

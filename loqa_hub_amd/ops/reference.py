@@ -431,6 +431,184 @@ def pack_mask(bits: torch.Tensor) -> torch.Tensor:
     return w.to(torch.int32)
 
 
+# ----------------------------------------------------------------- beam search
+# Whisper's BeamSearchDecoder + MaximumLikelihoodRanker (patience 1, no length
+# penalty). One order ranks candidates: higher score first, then the lower
+# source beam, then the lower column.
+def beam_topk(logits, mask=None, mask_rows=None, eot: int = -1, KB: int = 1):
+    """Per row of ``logits`` [R, V]: ``cand_id`` int32 [R, KB], the KB allowed
+    non-EOT columns of largest logit, descending, ties to the lower column, -1
+    past the allowed count; ``cand_lp`` f32 [R, KB], their log-softmax over all
+    allowed columns (EOT included; -inf past the count); ``eot_lp`` f32 [R],
+    EOT's (-inf when the mask forbids it or ``eot`` is no column)."""
+    x = logits.float().cpu()
+    R, V = x.shape
+    allowed = torch.ones(R, V, dtype=torch.bool)
+    if mask is not None:
+        m = mask if mask_rows is None else mask[mask_rows.long()]
+        allowed = unpack_mask(m.cpu(), V)[:R]
+    xm = x.masked_fill(~allowed, float("-inf"))
+    lsm = torch.log_softmax(xm, dim=-1)
+    lsm = torch.where(torch.isinf(xm) & (xm < 0), torch.full_like(lsm, float("-inf")), lsm)
+    cand_id = np.full((R, KB), -1, np.int32)
+    cand_lp = np.full((R, KB), -np.inf, np.float32)
+    eot_lp = np.full(R, -np.inf, np.float32)
+    xn, ln, an = xm.numpy(), lsm.numpy(), allowed.numpy()
+    for r in range(R):
+        cols = np.nonzero(an[r])[0]
+        if 0 <= eot < V and an[r, eot]:
+            eot_lp[r] = ln[r, eot]
+            cols = cols[cols != eot]
+        order = cols[np.lexsort((cols, -xn[r, cols]))][:KB]
+        cand_id[r, :len(order)] = order
+        cand_lp[r, :len(order)] = ln[r, order]
+    dev = logits.device
+    return (torch.from_numpy(cand_id).to(dev), torch.from_numpy(cand_lp).to(dev),
+            torch.from_numpy(eot_lp).to(dev))
+
+
+def beam_merge(cand_id, cand_lp, eot_lp, cum_in, n_src: int):
+    """Per group g of ``cum_in`` [G, B]: the B best of the ``n_src * B``
+    candidates of rows ``g * n_src ..`` by the f32 sum ``cum_in[g, src] +
+    cand_lp``. Returns (tok, parent, lp, cum_out, eot_score, eot_fin), each
+    [G, B]: missing candidates give tok = parent = -1 and lp = cum_out = -inf;
+    ``eot_score = cum_in + eot_lp`` (-inf past ``n_src``); ``eot_fin`` = 1 for
+    a source beam whose eot_score is strictly above ``cum_out[g, B - 1]``, or
+    when fewer than B candidates exist."""
+    dev = cum_in.device
+    cid = cand_id.cpu().numpy()
+    clp = cand_lp.cpu().numpy().astype(np.float32)
+    elp = eot_lp.cpu().numpy().astype(np.float32)
+    cum = cum_in.cpu().numpy().astype(np.float32)
+    G, B = cum.shape
+    assert n_src in (1, B) and cid.shape == (G * n_src, B)
+    tok = np.full((G, B), -1, np.int32)
+    parent = np.full((G, B), -1, np.int32)
+    lp = np.full((G, B), -np.inf, np.float32)
+    cum_out = np.full((G, B), -np.inf, np.float32)
+    eot_score = np.full((G, B), -np.inf, np.float32)
+    eot_fin = np.zeros((G, B), np.int32)
+    with np.errstate(invalid="ignore"):
+        for g in range(G):
+            cands = []
+            for s in range(n_src):
+                for j in range(B):
+                    c = int(cid[g * n_src + s, j])
+                    if c >= 0:
+                        l = clp[g * n_src + s, j]
+                        cands.append((np.float32(cum[g, s] + l), s, c, l))
+            cands.sort(key=lambda t: (-float(t[0]), t[1], t[2]))
+            for i, (sc, s, c, l) in enumerate(cands[:B]):
+                tok[g, i], parent[g, i], lp[g, i], cum_out[g, i] = c, s, l, sc
+            for s in range(n_src):
+                eot_score[g, s] = np.float32(cum[g, s] + elp[g * n_src + s])
+                eot_fin[g, s] = int(len(cands) < B or eot_score[g, s] > cum_out[g, B - 1])
+    t = lambda a: torch.from_numpy(a).to(dev)
+    return t(tok), t(parent), t(lp), t(cum_out), t(eot_score), t(eot_fin)
+
+
+class BeamState:
+    """Host side of one beam search (one 30 s window): the live beams' tokens
+    and log-probabilities, their cumulative scores (the next ``cum_in`` row) and
+    the finished hypotheses, advanced by one ``beam_merge`` result per step.
+    The first step has one source row (``n_src == 1``), later ones B."""
+
+    def __init__(self, B: int, eot: int, max_new: int):
+        self.B, self.eot, self.max_new = int(B), int(eot), int(max_new)
+        self.beams = [([], [])]
+        self.cum = np.full(self.B, -np.inf, np.float32)
+        self.cum[0] = 0.0
+        self.finished: list = []        # (tokens, sum_logprob, logprobs), EOT included
+        # per beam / finished hypothesis, the source row that produced each token
+        self.trace: list = [[]]
+        self.finished_trace: list = []
+        self.steps = 0
+        self.done = self.max_new <= 0
+
+    @property
+    def n_src(self) -> int:
+        return len(self.beams)
+
+    def advance(self, tok, parent, lp, cum_out, eot_score, eot_fin, eot_lp) -> list:
+        """One step's merge outputs (rows of length B; ``eot_lp``: n_src):
+        EOT extensions that finish join ``finished`` best first until B are
+        held, the selected extensions become the beams. Returns the new beams'
+        parents. ``done``: B finished, ``max_new`` steps, or fewer than B
+        extensions exist."""
+        new = []
+        for j, (t, l) in enumerate(self.beams):
+            if int(eot_fin[j]) and float(eot_score[j]) > -np.inf:
+                new.append((t + [self.eot], float(eot_score[j]), l + [float(eot_lp[j])]))
+                new[-1] += (self.trace[j] + [j],)
+        new.sort(key=lambda h: -h[1])       # stable: equal scores keep beam order
+        for h in new:
+            if len(self.finished) >= self.B:
+                break
+            self.finished.append(h[:3])
+            self.finished_trace.append(h[3])
+        live = [i for i in range(self.B) if int(tok[i]) >= 0]
+        old = self.beams
+        self.beams = [(old[int(parent[i])][0] + [int(tok[i])],
+                       old[int(parent[i])][1] + [float(lp[i])]) for i in live]
+        self.trace = [self.trace[int(parent[i])] + [int(parent[i])] for i in live]
+        self.cum = np.asarray(cum_out, np.float32).copy()
+        self.steps += 1
+        self.done = len(self.finished) >= self.B or self.steps >= self.max_new or \
+            len(live) < self.B
+        return [int(parent[i]) for i in live]
+
+    def result(self) -> tuple[list, int]:
+        """(hypotheses, winner index): the finished hypotheses, filled up to B
+        with the live beams in score order at their current sum; the winner
+        maximises sum_logprob / max(1, tokens without EOT) (the first maximum)."""
+        hyps = list(self.finished)
+        self.result_trace = list(self.finished_trace)
+        for i, (t, l) in enumerate(self.beams):
+            if len(hyps) >= self.B:
+                break
+            hyps.append((list(t), float(self.cum[i]), list(l)))
+            self.result_trace.append(list(self.trace[i]))
+        score = [s / max(1, sum(1 for x in t if x != self.eot)) for t, s, _ in hyps]
+        return hyps, (int(np.argmax(score)) if hyps else -1)
+
+
+def beam_search(step_fn, B: int, eot: int, max_new: int, mask=None):
+    """The whole search over ``step_fn(prefix) -> logits row [V]`` (``prefix``:
+    the list of tokens sampled so far). Returns (hypotheses, winner index), a
+    hypothesis = (tokens, sum_logprob, logprobs)."""
+    st = BeamState(B, eot, max_new)
+    while not st.done:
+        rows = torch.stack([torch.as_tensor(step_fn(list(t))).float() for t, _ in st.beams])
+        rm = None if mask is None else torch.zeros(len(rows), dtype=torch.int32)
+        cid, clp, elp = beam_topk(rows, mask, rm, eot, B)
+        out = beam_merge(cid, clp, elp, torch.from_numpy(st.cum)[None], st.n_src)
+        st.advance(*(o[0].numpy() for o in out), elp.numpy())
+    return st.result()
+
+
+def kv_copy_blocks(k, v, pairs) -> None:
+    """``k[:, dst] = k[:, src]`` (and ``v``) for every (src, dst) of ``pairs``;
+    sources and destinations are disjoint (``check_copy_pairs``)."""
+    if not len(pairs):
+        return
+    p = torch.as_tensor(pairs, dtype=torch.long, device=k.device).reshape(-1, 2)
+    k[:, p[:, 1]] = k[:, p[:, 0]]
+    v[:, p[:, 1]] = v[:, p[:, 0]]
+
+
+def check_copy_pairs(pairs, num_blocks: int) -> np.ndarray:
+    """``pairs`` as int32 [P, 2] (source block, destination block): every index
+    inside the cache, no destination twice, no block both read and written."""
+    p = np.asarray(pairs, np.int64).reshape(-1, 2)
+    if p.size and (p.min() < 0 or p.max() >= num_blocks):
+        raise ValueError(f"kv_copy_blocks: block index outside [0, {num_blocks})")
+    if len(set(p[:, 1].tolist())) != len(p):
+        raise ValueError("kv_copy_blocks: a destination block appears twice")
+    if set(p[:, 0].tolist()) & set(p[:, 1].tolist()):
+        raise ValueError("kv_copy_blocks: source and destination blocks overlap")
+    return p.astype(np.int32)
+
+
 def _pcm16_to_f32(pcm):
     """x / 32767 as the kernels compute it: one f32 multiply by the f32 nearest
     to 1 / 32767 (within one f32 ulp of the quotient; ``pcm.float() / 32767``

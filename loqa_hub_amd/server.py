@@ -122,7 +122,7 @@ def build_gpu_processor(cfg: Config, nats, device: str = "cuda:0", tts=None, *, 
                     temperatures=tuple(g.stt_temperature),
                     compression_ratio_threshold=g.stt_compression_ratio_threshold,
                     word_timestamps=g.stt_word_timestamps == "on",
-                    alignment_heads=g.stt_alignment_heads or None)
+                    alignment_heads=g.stt_alignment_heads or None, beam_size=g.stt_beam_size)
     if llm is None:
         llm = LLMEngine(lcfg, device, seed=g.seed, max_seqs=g.max_batch, weights=lw,
                         max_seq_len=g.max_seq_len, block_size=g.kv_block, use_graphs=g.use_graphs,
