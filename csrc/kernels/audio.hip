@@ -1,11 +1,12 @@
 // Whisper audio front-end on the GPU (SURVEY §2.4 K2 log_mel, K3 conv1d stem).
 //
-// log_mel: the STFT is a GEMM. Each 256-thread workgroup owns 32 frames of one
-// utterance: the reflect-padded, Hann-windowed frames are staged in LDS, then
-// the four waves run exact-f32 MFMA (v_mfma_f32_32x32x2_f32, guide §3 "FP32-input
-// MFMA" - log-mel needs f32 dynamic range, bf16 would not do) against the
-// cos/sin DFT basis, square-sum to the power spectrum in LDS, and project onto
-// the mel filterbank with a second f32 MFMA. log10 + per-utterance max are fused
+// log_mel: the STFT is a GEMM. Each 512-thread workgroup (8 waves) owns 32
+// frames of one utterance: the reflect-padded, Hann-windowed frames are staged
+// in LDS, then seven waves run exact-f32 MFMA (v_mfma_f32_32x32x2_f32, guide §3
+// "FP32-input MFMA" - log-mel needs f32 dynamic range, bf16 would not do)
+// against the cos/sin DFT basis, one 32-bin tile each, square-sum to the power
+// spectrum in LDS, and up to four waves project onto the mel filterbank with a
+// second f32 MFMA. log10 + per-utterance max are fused
 // into the epilogue; a tiny second kernel applies whisper's max-8 clamp and
 // (x + 4) / 4 scaling and emits bf16.
 //

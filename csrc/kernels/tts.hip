@@ -20,7 +20,7 @@ __global__ __launch_bounds__(64) void relpos_attention_kernel(
   __shared__ float p[RP_MAXT];
   __shared__ float qs[256];
   const int i = blockIdx.x, h = blockIdx.y, b = blockIdx.z, lane = threadIdx.x;
-  const int len = lens ? lens[b] : T;
+  const int len = lens ? min(lens[b], T) : T;
   const int C = H * D;
   const bf16_t* base = qkv + (size_t)b * T * ldq;
   bf16_t* orow = out + ((size_t)b * T + i) * ldo + h * D;
@@ -59,12 +59,14 @@ __global__ __launch_bounds__(64) void relpos_attention_kernel(
   sum = wave_sum(sum);
   const float inv = 1.f / sum;
   __syncthreads();
+  // keys j >= len have p[j] = 0 (exp(-1e4 - mx) underflows): they are skipped,
+  // not multiplied, so whatever a padded row holds (NaN too) stays out
   for (int d = lane; d < D; d += 64) {
     float acc = 0.f;
-    for (int j = 0; j < T; ++j) acc += p[j] * bf2f(base[(size_t)j * ldq + 2 * C + h * D + d]);
+    for (int j = 0; j < len; ++j) acc += p[j] * bf2f(base[(size_t)j * ldq + 2 * C + h * D + d]);
     for (int r = -window; r <= window; ++r) {
       const int j = i + r;
-      if (j >= 0 && j < T) acc += p[j] * bf2f(emb_v[(size_t)(r + window) * D + d]);
+      if (j >= 0 && j < len) acc += p[j] * bf2f(emb_v[(size_t)(r + window) * D + d]);
     }
     orow[d] = f2bf(acc * inv);
   }

@@ -1731,6 +1731,11 @@ def relpos_attention(qkv: torch.Tensor, emb_k: torch.Tensor, emb_v: torch.Tensor
         return ref.relpos_attention(qkv, emb_k, emb_v, lens, n_heads, head_dim, window,
                                     scale).to(torch.bfloat16)
     assert qkv.dtype == torch.bfloat16 and qkv.stride(-1) == 1
+    # the kernel addresses row (b, i) at (b * T + i) * ld: no batch stride of its own
+    assert B == 1 or qkv.stride(0) == T * qkv.stride(1), "qkv: batch stride must be T * row stride"
+    assert lens is None or (lens.dtype == torch.int32 and lens.device == qkv.device
+                            and lens.is_contiguous() and lens.numel() == B), \
+        "lens: int32 [B] on the device of qkv"
     out = torch.empty(B, T, n_heads * head_dim, dtype=torch.bfloat16, device=qkv.device)
     check(kernels().loqa_relpos_attention(ptr(qkv), qkv.stride(1), ptr(emb_k), ptr(emb_v),
                                           ptr(lens), ptr(out), out.stride(1), B, T, n_heads,

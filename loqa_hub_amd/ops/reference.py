@@ -815,14 +815,20 @@ class MelConstants:
         return cache[key]
 
 
-def log_mel(audio: torch.Tensor, c: MelConstants) -> torch.Tensor:
-    """Whisper log-mel (whisper/audio.py semantics) in fp32: [B, n_mels, n//160]."""
+def log_mel_db(audio: torch.Tensor, c: MelConstants) -> torch.Tensor:
+    """log10 of the clamped mel power spectrum in fp32, before Whisper's
+    max - 8 floor and scaling: [B, n_mels, n//160]."""
     win = c.window.to(audio.device)
     st = torch.stft(audio.float(), 400, 160, window=win, return_complex=True, center=True,
                     pad_mode="reflect")
     mag = st[..., :-1].abs() ** 2
     mel = c.filters.to(audio.device) @ mag
-    lg = torch.clamp(mel, min=1e-10).log10()
+    return torch.clamp(mel, min=1e-10).log10()
+
+
+def log_mel(audio: torch.Tensor, c: MelConstants) -> torch.Tensor:
+    """Whisper log-mel (whisper/audio.py semantics) in fp32: [B, n_mels, n//160]."""
+    lg = log_mel_db(audio, c)
     mx = lg.amax(dim=(-2, -1), keepdim=True)
     lg = torch.maximum(lg, mx - 8.0)
     return (lg + 4.0) / 4.0
@@ -1076,11 +1082,15 @@ def conv_transpose1d(x, w, bias=None, *, stride, padding, pre_slope=None):
 def relpos_attention(qkv, emb_k, emb_v, lens, H, D, window, scale):
     B, T, _ = qkv.shape
     C = H * D
+    idx = torch.arange(T, device=qkv.device)
+    L = lens.to(qkv.device) if lens is not None else torch.full((B,), T, device=qkv.device)
+    valid = idx[None, :] < L[:, None]
+    # rows at or past lens[b] are never read: whatever they hold (NaN too) stays out
+    qkv = torch.where(valid[..., None], qkv, torch.zeros((), dtype=qkv.dtype, device=qkv.device))
     q = qkv[..., :C].float().view(B, T, H, D).transpose(1, 2) * scale
     k = qkv[..., C:2 * C].float().view(B, T, H, D).transpose(1, 2)
     v = qkv[..., 2 * C:3 * C].float().view(B, T, H, D).transpose(1, 2)
     s = q @ k.transpose(-1, -2)
-    idx = torch.arange(T, device=qkv.device)
     rel = idx[None, :] - idx[:, None]
     inwin = rel.abs() <= window
     ek = emb_k.float()
@@ -1088,8 +1098,6 @@ def relpos_attention(qkv, emb_k, emb_v, lens, H, D, window, scale):
     ridx = (rel + window).clamp(0, 2 * window)
     s = s + torch.where(inwin, rl.gather(-1, ridx[None, None].expand(B, H, T, T)),
                         torch.zeros((), device=qkv.device))
-    L = lens.to(qkv.device) if lens is not None else torch.full((B,), T, device=qkv.device)
-    valid = idx[None, :] < L[:, None]
     m = valid[:, None, :, None] & valid[:, None, None, :]
     s = s.masked_fill(~m, -1e4)
     p = torch.softmax(s, -1)
@@ -1098,7 +1106,7 @@ def relpos_attention(qkv, emb_k, emb_v, lens, H, D, window, scale):
     pr = torch.zeros(B, H, T, 2 * window + 1, device=qkv.device)
     pr.scatter_add_(-1, ridx[None, None].expand(B, H, T, T), pw)
     o = o + pr @ emb_v.float()
-    o = o * valid[:, None, :, None]
+    o = torch.where(valid[:, None, :, None], o, torch.zeros((), device=qkv.device))     # +0.0, never -0.0
     return o.transpose(1, 2).reshape(B, T, C)
 
 
@@ -1115,6 +1123,42 @@ def expand_sample(stats, cum, flen, F, noise_scale, noise=None):
         e = noise[b, :n].float() if noise is not None else torch.zeros_like(m)
         z[b, :n] = m + e * torch.exp(lg) * noise_scale
     return z
+
+
+def hash32(x: np.ndarray) -> np.ndarray:
+    """The integer mixer of ``expand_sample`` (tts.hip ``hash32``), uint32."""
+    x = x.astype(np.uint32)
+    x = x ^ (x >> np.uint32(16))
+    x = x * np.uint32(0x7FEB352D)
+    x = x ^ (x >> np.uint32(15))
+    x = x * np.uint32(0x846CA68B)
+    return x ^ (x >> np.uint32(16))
+
+
+def gauss_uniforms(seed: int, B: int, F: int, C: int):
+    """The integer part of the device noise of ``expand_sample``, exactly:
+    ``(a, u1, u2)`` [B, F, C] - the first hash (uint32) and the two f32
+    uniforms, ``u1`` in (0, 1], ``u2`` in [0, 1). The noise of (row, frame,
+    channel) does not depend on B or F."""
+    b = np.arange(B, dtype=np.uint64)[:, None, None]
+    f = np.arange(F, dtype=np.uint64)[None, :, None]
+    c = np.arange(C, dtype=np.uint64)[None, None, :]
+    idx = ((b << np.uint64(24)) + f) * np.uint64(C) + c
+    lo = (idx & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+    hi = (idx >> np.uint64(32)).astype(np.uint32)
+    a = hash32(np.uint32(seed & 0xFFFFFFFF) ^ hash32(lo ^ np.uint32(0x9E3779B9)) ^ hi)
+    c2 = hash32(a ^ np.uint32(0x85EBCA6B))
+    # 1.0f / 16777217.0f: the divisor is no f32 and rounds to 2**24
+    u1 = ((a >> np.uint32(8)) + np.uint32(1)).astype(np.float32) * np.float32(2.0 ** -24)
+    u2 = (c2 >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
+    return a, u1, u2
+
+
+def gauss_noise(seed: int, B: int, F: int, C: int) -> np.ndarray:
+    """Host model of the device noise of ``expand_sample`` [B, F, C], fp64:
+    the hashes and both uniforms bit for bit, Box-Muller in fp64 from them."""
+    _, u1, u2 = gauss_uniforms(seed, B, F, C)
+    return np.sqrt(-2.0 * np.log(u1.astype(np.float64))) * np.cos(2.0 * np.pi * u2.astype(np.float64))
 
 
 # ------------------------------------------------------------ fused decode GEMMs
