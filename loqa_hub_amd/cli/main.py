@@ -40,24 +40,33 @@ def _tp_engine(cfg):
 
 async def run(cfg, tp_leader=None) -> None:
     from ..server import (HubServer, build_dp_processor, build_gpu_processor, build_service_processor,
-                          build_tts)
+                          build_tts, resolve_hotwords)
     server = HubServer(cfg)
     await server._connect_nats()
     processor = None
     use_gpu = cfg.gpu.llm_backend == "gpu" and cfg.gpu.stt_backend == "gpu"
+    # the STT hotwords, resolved once here for every engine the hub builds; the
+    # skill manifests' keywords need the skills loaded first
+    hot = []
+    if cfg.gpu.hotwords_on:
+        if cfg.gpu.stt_hotwords_skills == "on":
+            await server.load_skills()
+        hot = resolve_hotwords(cfg, server.skills)
     if tp_leader is not None:
         info, eng = tp_leader
         processor = build_gpu_processor(cfg, server.nats, device=str(info.device), tts="auto",
-                                        skills=server.skills, llm=eng)
+                                        skills=server.skills, llm=eng, hotwords=hot)
     elif use_gpu:
         import torch
         n = torch.cuda.device_count()
         want = cfg.gpu.dp or cfg.gpu.num_gpus or 1
         if n > 1 and want > 1:
             processor = await build_dp_processor(
-                cfg, min(n, want), server.nats.url if server.nats is not None else "")
+                cfg, min(n, want), server.nats.url if server.nats is not None else "",
+                hotwords=hot)
         elif n > 0:
-            processor = build_gpu_processor(cfg, server.nats, tts="auto", skills=server.skills)
+            processor = build_gpu_processor(cfg, server.nats, tts="auto", skills=server.skills,
+                                            hotwords=hot)
         else:
             log.warning("no GPU visible; using the external STT/LLM services")
     if processor is None:

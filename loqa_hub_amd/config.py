@@ -15,6 +15,7 @@ Durations use Go syntax (``300ms``, ``1h30m``, ``2s``).
 """
 from __future__ import annotations
 
+import math
 import os
 import re
 from dataclasses import dataclass, field
@@ -23,6 +24,13 @@ from dataclasses import dataclass, field
 # relay may record at (HUB_AUDIO_INPUT_RATE=relay) and a reply may be played at
 # (HUB_TTS_SAMPLE_RATE)
 AUDIO_SAMPLE_RATES = (8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000)
+
+# limits of the STT hotword list (engine/hotwords.py): phrases, and tokens per
+# token variant of a phrase. ``validate`` holds the list to the first; the
+# second needs the STT tokenizer (``GPUConfig.check_hotwords``, and again when the
+# engine compiles the list at start-up)
+HOTWORD_MAX_PHRASES = 1024
+HOTWORD_MAX_TOKENS = 16
 
 _DUR_RE = re.compile(r"([0-9]*\.?[0-9]+)(ns|us|µs|ms|s|m|h)")
 _UNIT = {"ns": 1e-9, "us": 1e-6, "µs": 1e-6, "ms": 1e-3, "s": 1.0, "m": 60.0, "h": 3600.0}
@@ -249,6 +257,19 @@ class GPUConfig:
     # hypotheses per freely decoded 30 s window, 1 = off (greedy). Not together
     # with stt_timestamps, stt_word_timestamps or a temperature fallback list.
     stt_beam_size: int = 1
+    # hotword biasing on the gpu backend: phrases (device, room and product
+    # names) whose tokens get stt_hotword_boost added to their logit, once per
+    # decoder step, while the decoded text is inside one of them (an
+    # Aho-Corasick automaton matched on the device). stt_hotwords holds
+    # HUB_STT_HOTWORDS merged with the lines of stt_hotwords_file;
+    # stt_hotwords_skills = on adds the keywords of the loaded skill manifests
+    # at start-up. The boost is in logit units and may be negative; its default
+    # is the context-score convention of shallow-fusion biasing, not a measured
+    # optimum. Not together with stt_beam_size > 1.
+    stt_hotwords: list = field(default_factory=list)
+    stt_hotwords_file: str = ""
+    stt_hotword_boost: float = 2.0
+    stt_hotwords_skills: str = "off"  # off | on
     # relay audio: "fixed" (every chunk is 16 kHz, AudioChunk.sample_rate is
     # ignored: the reference's behaviour) or "relay" (the stream's own rate, one
     # of AUDIO_SAMPLE_RATES; the gpu STT resamples it to 16 kHz on the device,
@@ -305,6 +326,42 @@ class GPUConfig:
             return load_tokenizer(explicit, vocab_size)
         ckpt = getattr(self, f"{which}_checkpoint")
         return load_tokenizer(ckpt, vocab_size) if find_tokenizer(ckpt) else None
+
+    @property
+    def hotwords_on(self) -> bool:
+        """Hotword biasing is configured (a phrase list or the skills source)."""
+        return bool(self.stt_hotwords) or self.stt_hotwords_skills == "on"
+
+    def resolve_hotwords(self, manifests=()) -> list:
+        """The one plain list every STT engine of the hub gets: stt_hotwords,
+        then (stt_hotwords_skills = on) the ``keywords`` of ``manifests`` in
+        order; phrases normalised, duplicates collapsed, held to the phrase
+        limit."""
+        out = list(self.stt_hotwords)
+        if self.stt_hotwords_skills == "on":
+            for m in manifests:
+                out += [str(k) for k in (getattr(m, "keywords", None) or [])]
+        out = _hotword_list(out)
+        if len(out) > HOTWORD_MAX_PHRASES:
+            raise ConfigError(f"invalid configuration: {len(out)} STT hotwords (HUB_STT_HOTWORDS, "
+                              "HUB_STT_HOTWORDS_FILE and skill keywords) exceed the limit of "
+                              f"{HOTWORD_MAX_PHRASES}: {out[HOTWORD_MAX_PHRASES]!r}")
+        return out
+
+    def check_hotwords(self, phrases, encode=None, vocab_size: int | None = None) -> None:
+        """``phrases`` against the limits that need the STT tokenizer (tokens per
+        variant, token ids within the vocabulary, the table's capacity); the
+        hub's start-up calls it on the resolved list. ``encode`` / ``vocab_size``
+        default to the configured STT model's tokenizer."""
+        from .engine.hotwords import compile_hotwords
+        if encode is None:
+            from .engine.tokenizer import get_tokenizer
+            vocab_size = self.stt_config().vocab_size
+            encode = (self.tokenizer("stt", vocab_size) or get_tokenizer(vocab_size)).encode
+        try:
+            compile_hotwords(phrases, self.stt_hotword_boost, encode, vocab_size)
+        except ValueError as e:
+            raise ConfigError(f"invalid configuration: HUB_STT_HOTWORDS: {e}") from None
 
 
 @dataclass
@@ -443,6 +500,23 @@ class Config:
             if b > self.gpu.max_batch:
                 raise ConfigError(f"HUB_STT_BEAM_SIZE {b} exceeds HUB_MAX_BATCH "
                                   f"{self.gpu.max_batch} (decoder rows)")
+        if self.gpu.stt_hotwords_skills not in ("off", "on"):
+            raise ConfigError("invalid HUB_STT_HOTWORDS_SKILLS (off | on): "
+                              f"{self.gpu.stt_hotwords_skills}")
+        hb = self.gpu.stt_hotword_boost
+        if not (math.isfinite(hb) and abs(hb) <= 3.4028234663852886e38):
+            raise ConfigError(f"HUB_STT_HOTWORD_BOOST must be a finite f32 number: {hb}")
+        if len(self.gpu.stt_hotwords) > HOTWORD_MAX_PHRASES:
+            raise ConfigError(f"HUB_STT_HOTWORDS: {len(self.gpu.stt_hotwords)} phrases exceed the "
+                              f"limit of {HOTWORD_MAX_PHRASES}: "
+                              f"{self.gpu.stt_hotwords[HOTWORD_MAX_PHRASES]!r}")
+        if self.gpu.hotwords_on:
+            if self.gpu.stt_backend != "gpu":
+                raise ConfigError("HUB_STT_HOTWORDS / HUB_STT_HOTWORDS_SKILLS need "
+                                  f"HUB_STT_BACKEND=gpu: {self.gpu.stt_backend}")
+            if b > 1:
+                raise ConfigError("HUB_STT_BEAM_SIZE > 1 does not combine with HUB_STT_HOTWORDS "
+                                  "(beams carry no hotword state)")
         if not self.gpu.stt_compression_ratio_threshold > 0.0:
             raise ConfigError("HUB_STT_COMPRESSION_RATIO_THRESHOLD must be > 0: "
                               f"{self.gpu.stt_compression_ratio_threshold}")
@@ -516,6 +590,35 @@ def _beam_size(e) -> int:
     if not re.fullmatch(r"[+-]?\d+", v):
         raise ConfigError(f"invalid configuration: invalid HUB_STT_BEAM_SIZE: {v}")
     return int(v)
+
+
+def _hotword_list(phrases) -> list:
+    """Phrases stripped, their inner whitespace collapsed, empty ones dropped,
+    duplicates collapsed (the first kept)."""
+    out, seen = [], set()
+    for p in phrases:
+        p = " ".join(str(p).split())
+        if p and p not in seen:
+            seen.add(p)
+            out.append(p)
+    return out
+
+
+def _hotwords(e) -> list:
+    """HUB_STT_HOTWORDS (a comma list) merged with the lines of
+    HUB_STT_HOTWORDS_FILE (one phrase per line; blank lines and lines that
+    start with ``#`` are skipped)."""
+    out = env_str(e, "", "HUB_STT_HOTWORDS").split(",")
+    path = env_str(e, "", "HUB_STT_HOTWORDS_FILE").strip()
+    if path:
+        try:
+            with open(path, encoding="utf-8") as f:
+                lines = f.read().splitlines()
+        except OSError as err:
+            raise ConfigError("invalid configuration: cannot read HUB_STT_HOTWORDS_FILE "
+                              f"{path}: {err.strerror or err}") from None
+        out += [ln for ln in lines if ln.strip() and not ln.lstrip().startswith("#")]
+    return _hotword_list(out)
 
 
 def load(env=None) -> Config:
@@ -607,6 +710,10 @@ def load(env=None) -> Config:
             stt_word_timestamps=env_str(e, "off", "HUB_STT_WORD_TIMESTAMPS").strip().lower(),
             stt_alignment_heads="".join(env_str(e, "", "HUB_STT_ALIGNMENT_HEADS").split()),
             stt_beam_size=_beam_size(e),
+            stt_hotwords=_hotwords(e),
+            stt_hotwords_file=env_str(e, "", "HUB_STT_HOTWORDS_FILE").strip(),
+            stt_hotword_boost=_strict_float(e, 2.0, "HUB_STT_HOTWORD_BOOST"),
+            stt_hotwords_skills=env_str(e, "off", "HUB_STT_HOTWORDS_SKILLS").strip().lower(),
             stt_compression_ratio_threshold=_strict_float(e, 2.4,
                                                           "HUB_STT_COMPRESSION_RATIO_THRESHOLD"),
             audio_input_rate=env_str(e, "fixed", "HUB_AUDIO_INPUT_RATE").lower(),

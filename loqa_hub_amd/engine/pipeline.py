@@ -55,6 +55,7 @@ class PipelineJob:
     stt_failed: bool = False
     no_speech: bool = False                 # every window fell to the STT engine's no-speech rule
     stt_fallback: bool = False              # a window was decoded again at a higher temperature
+    stt_hotword: bool = False               # the transcript contains a configured hotword
     # STT engine with timestamps (else None): (start_s, end_s, text) segments in
     # utterance time, and the windows whose last segment was left open
     segments: list | None = None
@@ -158,8 +159,9 @@ class VoicePipeline:
             segments=r.segments, speech_start_s=r.speech_start_s, speech_end_s=r.speech_end_s,
             temperature=max(r.temperatures) if r.temperatures else None,
             compression_ratio=max(r.compression_ratios) if r.compression_ratios else None,
-            words=r.words)
+            words=r.words, hotwords=r.hotwords)
         j.stt_fallback = r.fallback_attempts > 0
+        j.stt_hotword = bool(r.hotwords)
         j.segments, j.open_segments = r.segments, r.open_segments
         j.words = r.words
         j.no_speech = r.gated_windows > 0 and r.gated_windows == r.windows

@@ -16,6 +16,7 @@ import os
 import queue
 import threading
 import time
+import weakref
 import zlib
 from concurrent.futures import FIRST_COMPLETED, Future, ThreadPoolExecutor, wait
 from dataclasses import dataclass, field
@@ -191,6 +192,10 @@ class STTRequest:
     # debug: per beam the tokens its row is made to follow (parents forced to
     # the identity), and per hypothesis the source row of each of its tokens
     beam_force: list | None = None
+    # STTEngine(hotwords=[...]) (None with the feature off): the phrases whose
+    # token sequence occurs in the kept windows' text tokens, in order of first
+    # occurrence
+    hotwords: list | None = None
     hypothesis_traces: list = field(default_factory=list)
 
 
@@ -215,8 +220,24 @@ class STTEngine:
                  no_speech_threshold: float = 0.6, logprob_threshold: float = -1.0,
                  timestamps: bool = False, max_initial_timestamp: float = 1.0,
                  temperatures=(0.0,), compression_ratio_threshold: float = 2.4,
-                 word_timestamps: bool = False, alignment_heads=None, beam_size: int = 1):
+                 word_timestamps: bool = False, alignment_heads=None, beam_size: int = 1,
+                 hotwords=None, hotword_boost: float = 2.0):
         self.cfg = cfg
+        # hotword biasing (engine/hotwords.py): every decoder step ends, before
+        # the sampler, with ops.hotword_step, which advances the sequence's node
+        # of the phrase automaton by the token it sampled last (``hw_state`` and
+        # ``last_tok``, per cross-attention slot on the device) and adds
+        # ``hotword_boost`` to the logit of every token the node expects. What
+        # the sampler reports (log-probabilities, the no-speech and fallback
+        # tests on them) is computed from the biased logits. None / empty: off,
+        # and fields, launches and results are the plain engine's.
+        from .hotwords import check_boost, normalize_phrases
+        hotwords = normalize_phrases(hotwords)
+        self.hotwords_on = bool(hotwords)
+        self.hotword_boost = check_boost(hotword_boost)
+        if self.hotwords_on and int(beam_size) > 1:
+            raise ValueError("STT beam_size > 1 does not combine with hotwords (hypotheses "
+                             "change rows; their hotword state does not follow them)")
         # beam search (engine/stt_beam.py): Whisper's BeamSearchDecoder with
         # patience 1 over ``beam_size`` hypotheses per freely decoded window,
         # selected on the device (ops.beam_topk / beam_merge), the KV moved
@@ -300,10 +321,14 @@ class STTEngine:
         if self.sot_probe:
             self._init_probe(language, languages)
             language = self.lang_codes[0]      # placeholder in ``sot``: fed per request
+        extra = ()
         if self.row_fields:
-            i = self.STEP_FIELDS.index("src")
             extra = ("mask_row", "probe") + (("ts_ctl",) if self.timestamps else ()) + \
                 (("temp", "rng") if self.fallback else ())
+        if self.hotwords_on:
+            extra += ("hw_ctl",)
+        if extra:
+            i = self.STEP_FIELDS.index("src")
             self.step_fields = self.STEP_FIELDS[:i] + extra + self.STEP_FIELDS[i:]
         # start-of-transcript prompt; the language token follows STT_LANGUAGE
         # (the reference passes it to its STT service)
@@ -369,6 +394,19 @@ class STTEngine:
             self.stats.update(fallback_windows=0, fallback_attempts=0)
         if self.beam_size > 1:
             self.stats.update(beam_windows=0, beam_kv_copies=0)
+        self.hw_table = self.hw_auto = None
+        self._live_reqs = None
+        if self.hotwords_on:
+            # the automaton node of every cross-attention slot (+ a trash slot,
+            # the last), beside ``last_tok``, which a hotword engine always keeps
+            self.stats.update(hotword_windows=0, hotword_matches=0)
+            # the requests being decoded (set_hotwords waits for none); weak, so
+            # a request its caller abandons does not count for ever
+            self._live_reqs = weakref.WeakSet()
+            self.hw_state = torch.zeros(max_batch + 1, dtype=torch.int32, device=self.device)
+            self.last_tok = torch.zeros(max_batch + 1, dtype=torch.int32, device=self.device)
+            self.hw_table = ops.HotwordTable(self.device)
+            self.set_hotwords(hotwords)
         if self.timestamps:
             # the rule state of every cross-attention slot (+ a trash slot, the
             # last, for padding rows), beside ``last_tok``
@@ -429,7 +467,8 @@ class STTEngine:
             # slot) feeds the device-fed greedy steps, and with ``token_logprobs``
             # the tokens' log-probabilities are published beside them
             b_max = next((b for b in self.SEQ_BUCKETS if b >= max_batch), self.SEQ_BUCKETS[-1])
-            self.last_tok = torch.zeros(max_batch + 1, dtype=torch.int32, device=self.device)
+            if not self.hotwords_on:
+                self.last_tok = torch.zeros(max_batch + 1, dtype=torch.int32, device=self.device)
             self.io = StepIO(self.device, self._layout(b_max, ops.MPADS[-1]), self.last_tok,
                              logprobs=2 if self.row_fields else token_logprobs)
         # two decoder steps in flight (the host prepares step j+1 while step j
@@ -477,8 +516,9 @@ class STTEngine:
     def _layout(self, B_pad: int, T_pad: int) -> StepLayout:
         """``step_layout`` of this engine (a probing one stages two more
         per-sequence fields, ``mask_row`` and ``probe``; a timestamps one those
-        and ``ts_ctl``; a temperature-fallback one ``temp`` and ``rng`` too)."""
-        if not self.row_fields:
+        and ``ts_ctl``; a temperature-fallback one ``temp`` and ``rng`` too; a
+        hotword one ``hw_ctl``)."""
+        if self.step_fields is self.STEP_FIELDS:
             return self.step_layout(B_pad, T_pad, self.max_blocks)
         return StepLayout(step_shapes(self.step_fields, B_pad, T_pad, self.max_blocks),
                           max(16, ops.mpad_for(B_pad)))
@@ -643,9 +683,10 @@ class STTEngine:
         request's ``feed``); ``out`` = preallocated views (a staging row) to
         fill in place and return. ``sot`` (probing engine): the requests whose
         feed ends in SOT this step (default: ``sot_pending`` and the whole
-        remaining prompt fed). ``ts_ctl`` (timestamps engine): the rows' rule
-        control words (default: ``_ts_ctl`` of a step that feeds every request's
-        whole remaining feed). ``samp`` (temperature fallback): the rows'
+        remaining prompt fed). ``ts_ctl`` (timestamps or hotword engine): the
+        rows' rule control words, staged as ``ts_ctl`` and / or ``hw_ctl``
+        (default: ``_ts_ctl`` of a step that feeds every request's whole
+        remaining feed). ``samp`` (temperature fallback): the rows'
         (temperature, random key) (default: ``_samp`` of such a step)."""
         T_enc = self.cfg.n_audio_ctx
         if feeds is None:
@@ -672,9 +713,18 @@ class STTEngine:
             mask_row[n:] = 0
             probe[:n] = [self.nospeech if x else -1 for x in sot]
             probe[n:] = -1
+        if (self.timestamps or self.hotwords_on) and ts_ctl is None:
+            ts_ctl = [self._ts_ctl(r, len(f) < len(r.feed)) for r, f in zip(live, feeds)]
+        if self.hotwords_on:
+            # the hotword control word is the timestamp rules': both say where
+            # in its window's free decoding the row's step is
+            if out is None:
+                host["hw_ctl"] = np.zeros(B_pad, np.int32)
+                host["row_slot"] = np.full(B_pad, self.max_batch, np.int32)
+                host["row_slot"][:n] = [r.slot for r in live]
+            host["hw_ctl"][:n] = ts_ctl
+            host["hw_ctl"][n:] = 0
         if self.timestamps:
-            if ts_ctl is None:
-                ts_ctl = [self._ts_ctl(r, len(f) < len(r.feed)) for r, f in zip(live, feeds)]
             if out is None:
                 # an eager step: the graphs' callers stage ``row_slot`` themselves
                 host["ts_ctl"] = np.zeros(B_pad, np.int32)
@@ -748,11 +798,15 @@ class STTEngine:
         """``_argmax``; a probing engine: (tokens, log-probabilities, probed
         log-probabilities) under each sequence's mask row, the probe read from
         the step's ``probe`` field."""
+        B = logits.shape[0]
+        if self.hotwords_on:
+            # in place on the step's logits: everything below sees them biased
+            ops.hotword_step(logits, logits.shape[1], dev["hw_ctl"][:B], dev["row_slot"][:B],
+                             self.hw_state, self.last_tok, self.hw_table)
         if not self.row_fields:
             return self._argmax(logits)
         if self._beam is not None:
             self._beam.logits = logits
-        B = logits.shape[0]
         if self.fallback:
             # the rules (when on) plus a per-row temperature and random key: a
             # row at temperature 0 is the greedy one, bit for bit
@@ -897,7 +951,7 @@ class STTEngine:
                 self._host_meta(live, B_pad, T_pad, out=hb, sot=sot, ts_ctl=ts_ctl, samp=samp)
                 hb["src"].fill(-1)
                 hb["row_slot"].fill(self.io.trash)
-                if self.timestamps or self.align is not None:
+                if self.timestamps or self.align is not None or self.hotwords_on:
                     # the rows' rule state / query store (and last_tok) slots
                     hb["row_slot"][:B] = [r.slot for r in live]
                 t1 = time.perf_counter()
@@ -908,12 +962,24 @@ class STTEngine:
                 self.stats["gpu_wait_s"] += time.perf_counter() - t1
                 return out
             max_q, host = self._host_meta(live, B_pad, T_pad, sot=sot, ts_ctl=ts_ctl, samp=samp)
-            return self._host(self._fast_forward(self._dev(host), max_q, B_pad), B)
+            res = self._fast_forward(self._dev(host), max_q, B_pad)
+            self._keep_last(live, res)
+            return self._host(res, B)
         if self.fallback:
             return self._eager_step(live, sot, ts_ctl, samp)
-        if self.timestamps:
+        if self.timestamps or self.hotwords_on:
             return self._eager_step(live, sot, ts_ctl)
         return self._eager_step(live, sot) if self.sot_probe else self._eager_step(live)
+
+    def _keep_last(self, live: list[STTRequest], res) -> None:
+        """A step outside the captured graphs has no publish node: a hotword
+        engine writes the sampled tokens to ``last_tok`` itself, where the next
+        step's ``ops.hotword_step`` reads them."""
+        if not self.hotwords_on:
+            return
+        tok = res[0] if isinstance(res, tuple) else res
+        idx = torch.tensor([r.slot for r in live], dtype=torch.long, device=self.device)
+        self.last_tok[idx] = tok[: len(live)].to(torch.int32)
 
     def _eager_step(self, live: list[STTRequest], sot: list | None = None,
                     ts_ctl: list | None = None, samp: list | None = None):
@@ -946,15 +1012,20 @@ class STTEngine:
             dev(cu, torch.int32), dev(ctx, torch.int32), dev(bt, torch.int32), max_q, max_ctx,
             self.kv.k, self.kv.v, self.xkv, enc_starts, enc_lens, dev(lidx, torch.int64), self.ws,
             align=al)
-        if not self.row_fields:
+        if not self.row_fields and not self.hotwords_on:
             return self._host(self._argmax(logits))
-        if sot is None:
-            sot = [r.sot_pending for r in live]
-        meta = {"mask_row": dev([1 if x else 0 for x in sot], torch.int32),
-                "probe": dev([self.nospeech if x else -1 for x in sot], torch.int32)}
+        meta = {}
+        if (self.timestamps or self.hotwords_on) and ts_ctl is None:
+            ts_ctl = [self._ts_ctl(r) for r in live]
+        if self.hotwords_on:
+            meta["hw_ctl"] = dev(list(ts_ctl), torch.int32)
+            meta["row_slot"] = dev([r.slot for r in live], torch.int32)
+        if self.row_fields:
+            if sot is None:
+                sot = [r.sot_pending for r in live]
+            meta["mask_row"] = dev([1 if x else 0 for x in sot], torch.int32)
+            meta["probe"] = dev([self.nospeech if x else -1 for x in sot], torch.int32)
         if self.timestamps:
-            if ts_ctl is None:
-                ts_ctl = [self._ts_ctl(r) for r in live]
             meta["ts_ctl"] = dev(list(ts_ctl), torch.int32)
             meta["row_slot"] = dev([r.slot for r in live], torch.int32)
         if self.fallback:
@@ -962,7 +1033,9 @@ class STTEngine:
                 samp = [self._samp(r) for r in live]
             meta["temp"] = dev([t for t, _ in samp], torch.float32).view(torch.int32)
             meta["rng"] = dev([k for _, k in samp], torch.int32)
-        return self._host(self._sample(logits, meta))
+        res = self._sample(logits, meta)
+        self._keep_last(live, res)
+        return self._host(res)
 
     # ----------------------------------------------------------- admission
     def _admit(self, reqs: list[STTRequest], slots: list[int],
@@ -1041,6 +1114,9 @@ class STTEngine:
                 r.sample_seed = ops.ref.sample_key(self.seed, self._seed_ctr, 0, 0)
             if self.timestamps:
                 r.segments, r.open_segments = [], []
+            r.hotwords = [] if self.hotwords_on else None
+            if self._live_reqs is not None:
+                self._live_reqs.add(r)
             if not r.slots:
                 r.slots = [r.slot]
             self._begin_window(r, 0)
@@ -1140,9 +1216,9 @@ class STTEngine:
         if self.fallback:
             nxt = self._step(live, [r.sot_pending and not x for r, x in zip(live, rest)],
                              [self._ts_ctl(r, bool(x)) for r, x in zip(live, rest)]
-                             if self.timestamps else None,
+                             if self.timestamps or self.hotwords_on else None,
                              [self._samp(r, bool(x)) for r, x in zip(live, rest)])
-        elif self.timestamps:
+        elif self.timestamps or self.hotwords_on:
             nxt = self._step(live, [r.sot_pending and not x for r, x in zip(live, rest)],
                              [self._ts_ctl(r, bool(x)) for r, x in zip(live, rest)])
         else:
@@ -1248,6 +1324,16 @@ class STTEngine:
         if self.align is not None and not gated:
             # a kept window (not gated, not a discarded fallback attempt)
             self._align_window(r, seg_of)
+        if self.hotwords_on and not gated:
+            # the phrases spelled out in a kept window's text tokens, found by
+            # the automaton the device walked (teacher-forced windows too, though
+            # only freely decoded ones were biased)
+            self.stats["hotword_windows"] += r.target is None
+            if self.hw_auto is not None:
+                new = [self.hw_auto.phrases[i] for i in self.hw_auto.matches(toks)]
+                new = [p for p in new if p not in r.hotwords]
+                r.hotwords += new
+                self.stats["hotword_matches"] += len(new)
         if r.logprobs and not gated:
             # fp64 sum of the window's f32 values; -inf (nothing allowed) stays -inf
             r.lp_sum += float(np.sum(np.asarray(r.logprobs, np.float64)))
@@ -1271,7 +1357,28 @@ class STTEngine:
                 self.stats["logprob_tokens"] += r.lp_n
                 self.stats["logprob_sum"] += r.lp_sum
         self.stats["utterances"] += 1
+        if self._live_reqs is not None:
+            self._live_reqs.discard(r)
         return r
+
+    def set_hotwords(self, phrases, boost: float | None = None) -> None:
+        """Replace the hotword list (and with ``boost`` the boost) of an engine
+        built with hotwords: the automaton is compiled on the host and written
+        into the device buffers the captured graphs already point at, so nothing
+        is captured again. An empty list makes the biasing step a no-op. Allowed
+        only while no request is being decoded (``RuntimeError`` otherwise): a
+        sequence's node belongs to the automaton it was advanced in."""
+        from .hotwords import check_boost, compile_hotwords
+        if not self.hotwords_on:
+            raise ValueError("set_hotwords: the engine was built without hotwords (its steps "
+                             "have no biasing launch)")
+        if self._live_reqs:
+            raise RuntimeError(f"set_hotwords: {len(self._live_reqs)} requests are live")
+        b = self.hotword_boost if boost is None else check_boost(boost)
+        auto = compile_hotwords(phrases, b, self.tok.encode, self.cfg.vocab_size)
+        self.hw_table.load(auto if auto.T else None)
+        self.hw_auto = auto if auto.T else None
+        self.hotword_boost = b
 
     def align_rows(self, r: STTRequest) -> tuple[list, list, int | None, int]:
         """What the alignment of ``r``'s current window reads: (``rows``, the
@@ -1521,6 +1628,8 @@ class STTEngine:
                     if not fut.done():
                         fut.set_exception(e)
                 live, waiting, cells, encoding = [], [], {}, []
+                if self._live_reqs is not None:
+                    self._live_reqs.clear()
                 self._free_slots = list(range(self.max_slots))
 
     def _encoder_executor(self) -> ThreadPoolExecutor:

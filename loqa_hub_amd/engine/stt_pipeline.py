@@ -167,12 +167,12 @@ class STTPipeline:
         return True
 
     def _ts_ctl(self, rows):
-        """A timestamps engine's rule control words for the rows' next steps,
+        """A timestamps or hotword engine's control words for the rows' next steps,
         from the launch counts alone (the host has not seen the tokens of the
         steps in flight): 0 = a prompt chunk before the last, the SOT probe step
         and every step of a teacher-forced window, 1 = the step feeding the
         window's last prompt token, 2 = later steps, whose state is on the device."""
-        if not self.eng.timestamps:
+        if not (self.eng.timestamps or self.eng.hotwords_on):
             return None
         return [0 if r.target is not None or r.pl_launched < r.prompt_steps - 1 else
                 1 if r.pl_launched == r.prompt_steps - 1 else 2 for r in rows]
@@ -209,10 +209,12 @@ class STTPipeline:
         for r, f in zip(rows, saved):
             r.feed = f
         # the eager step does not run the graphs' publish node: keep last_tok
-        # current for a following device-fed step
-        idx = torch.tensor([r.slot for r in rows], dtype=torch.long, device=self.eng.device)
-        self.eng.last_tok[idx] = torch.as_tensor(np.asarray(out, np.int32)[: len(rows)],
-                                                 device=self.eng.device)
+        # current for a following device-fed step (a hotword engine's step has
+        # written it already, ``STTEngine._keep_last``)
+        if not self.eng.hotwords_on:
+            idx = torch.tensor([r.slot for r in rows], dtype=torch.long, device=self.eng.device)
+            self.eng.last_tok[idx] = torch.as_tensor(np.asarray(out, np.int32)[: len(rows)],
+                                                     device=self.eng.device)
         entries = []
         for r in rows:
             entries.append((r.pl_launched, False))

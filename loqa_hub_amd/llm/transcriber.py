@@ -50,6 +50,9 @@ class TranscriptionResult:
     # without a wake word or without a word after it)
     words: list | None = None
     command_start_s: float | None = None
+    # HUB_STT_HOTWORDS (gpu backend; else None): the configured phrases that the
+    # decoder's text contains, in order of first occurrence
+    hotwords: list | None = None
 
 
 @dataclass
@@ -131,7 +134,8 @@ def to_transcription_result(raw: str, avg_logprob: float | None = None,
                             speech_end_s: float | None = None,
                             temperature: float | None = None,
                             compression_ratio: float | None = None,
-                            words: list | None = None) -> TranscriptionResult:
+                            words: list | None = None,
+                            hotwords: list | None = None) -> TranscriptionResult:
     """``avg_logprob`` (the on-device Whisper decode's mean token
     log-probability): the confidence is the geometric-mean token probability
     ``min(1, exp(avg_logprob))`` instead of the text heuristic, and a
@@ -143,11 +147,13 @@ def to_transcription_result(raw: str, avg_logprob: float | None = None,
     timestamps (their texts are the decoder's, before the wake-word cut), and
     ``temperature`` / ``compression_ratio`` of a decode with temperature fallback,
     and ``words`` of a decode with word timestamps, from which ``command_start_s``
-    (the wake-word cut in seconds) is read."""
+    (the wake-word cut in seconds) is read, and ``hotwords`` of a decode with
+    hotword biasing."""
     p = post_process_transcription(raw)
     probe = dict(language=language, language_prob=language_prob, no_speech_prob=no_speech_prob,
                  segments=segments, speech_start_s=speech_start_s, speech_end_s=speech_end_s,
                  temperature=temperature, compression_ratio=compression_ratio, words=words,
+                 hotwords=hotwords,
                  command_start_s=command_start(words, p.wake_word_variant)
                  if p.wake_word_detected else None)
     if avg_logprob is None:

@@ -588,6 +588,91 @@ def kv_copy_blocks(k: torch.Tensor, v: torch.Tensor, pairs) -> None:
                                         ptr(pd), len(p), stream_ptr(k)), "kv_copy_blocks")
 
 
+# ------------------------------------------------------------ hotword biasing
+HOTWORD_WG = 64     # workgroup size of hotword_step_kernel (csrc/kernels/hotword.hip)
+
+
+class HotwordTable:
+    """A hotword automaton (``engine.hotwords.HotwordAutomaton``) where
+    ``hotword_step`` reads it: on a GPU four int32 buffers (header, ``off``,
+    ``tok``, ``dst``) allocated once at the worst case of the limits, so that
+    captured graphs hold pointers that ``load`` rewrites in place; on the CPU
+    the automaton itself. ``auto`` None or without edges: the step is a no-op."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self.auto = None
+        self.hdr = self.off = self.tok = self.dst = None
+        if self.device.type == "cuda":
+            z = lambda n: torch.zeros(n, dtype=torch.int32, device=self.device)
+            self.hdr, self.off = z(4), z(ref.HOTWORD_N_CAP + 1)
+            self.tok, self.dst = z(ref.HOTWORD_T_CAP), z(ref.HOTWORD_T_CAP)
+
+    def load(self, auto) -> None:
+        """Make ``auto`` (None: no phrases) the table's automaton. The device
+        buffers are rewritten in place after the device has finished what was
+        launched; the caller keeps decoder steps from running meanwhile."""
+        if auto is not None and (auto.N > ref.HOTWORD_N_CAP or auto.T > ref.HOTWORD_T_CAP):
+            raise ValueError(f"hotword automaton of {auto.N} nodes / {auto.T} table entries exceeds "
+                             f"the buffers ({ref.HOTWORD_N_CAP} / {ref.HOTWORD_T_CAP})")
+        self.auto = auto
+        if self.hdr is None:
+            return
+        torch.cuda.synchronize(self.device)
+        self.hdr.zero_()            # an empty header first: N = T = 0 is the no-op
+        if auto is not None and auto.T > 0:
+            self.off[: auto.N + 1].copy_(torch.from_numpy(auto.off))
+            self.tok[: auto.T].copy_(torch.from_numpy(auto.tok))
+            self.dst[: auto.T].copy_(torch.from_numpy(auto.dst))
+            self.hdr.copy_(torch.from_numpy(auto.header()))
+        torch.cuda.synchronize(self.device)
+
+
+def hotword_step(logits: torch.Tensor, V: int, hw_ctl: torch.Tensor, row_slot: torch.Tensor,
+                 hw_state: torch.Tensor, last_tok: torch.Tensor, table: HotwordTable) -> None:
+    """One decoder step of hotword biasing, in place, before the sampler
+    (``ops.reference.hotword_step`` has the semantics and is the CPU path).
+    ``logits`` [B, >= V] f32 or bf16 with a row stride >= V; per row b with s =
+    ``row_slot[b]``: ``hw_ctl[b]`` 0 = untouched bit for bit, state included; 1
+    = the window's first freely sampled token, node 0; 2 = node
+    ``advance(hw_state[s], last_tok[s])``. The node is stored in ``hw_state[s]``
+    and the automaton's boost is added once to every column below ``V`` that
+    the node expects. The slots of ruled rows must differ and lie within
+    ``hw_state`` / ``last_tok`` (a ValueError when the fields are host tensors;
+    on the device a row whose slot is out of range is left alone)."""
+    if logits.dim() != 2 or logits.stride(-1) != 1 or not 0 < V <= logits.shape[1] or \
+            (logits.shape[0] > 1 and logits.stride(0) < V):
+        raise ValueError(f"hotword_step: logits {tuple(logits.shape)} (strides {logits.stride()}) "
+                         f"do not hold rows of {V} columns")
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"hotword_step: logits must be float32 or bfloat16, got {logits.dtype}")
+    B, dev = logits.shape[0], logits.device
+    for t, name in ((hw_ctl, "hw_ctl"), (row_slot, "row_slot")):
+        _i32(t, name, dev)
+        if t.numel() != B:
+            raise ValueError(f"hotword_step: {name} has {t.numel()} entries for {B} rows")
+    _i32(hw_state, "hw_state", dev)
+    _i32(last_tok, "last_tok", dev)
+    if table.device.type != dev.type:
+        raise ValueError(f"hotword_step: the table is on {table.device}, the logits on {dev}")
+    slots = min(hw_state.numel(), last_tok.numel())
+    if dev.type == "cpu" and B:
+        ruled = row_slot[(hw_ctl == 1) | (hw_ctl == 2)]
+        if ruled.numel() != ruled.unique().numel():
+            raise ValueError("hotword_step: two ruled rows share a state slot")
+        if ruled.numel() and not (0 <= int(ruled.min()) and int(ruled.max()) < slots):
+            raise ValueError(f"hotword_step: a ruled row's slot is outside the {slots} slots")
+    if not _gpu(logits):
+        return ref.hotword_step(logits, V, hw_ctl, row_slot, hw_state, last_tok, table.auto)
+    if B == 0:
+        return
+    check(kernels().loqa_hotword_step(
+        ptr(logits), int(logits.dtype == torch.bfloat16), logits.stride(0) if B > 1 else
+        max(logits.stride(0), V), B, V, ptr(hw_ctl), ptr(row_slot), ptr(hw_state), ptr(last_tok),
+        slots, ptr(table.hdr), ptr(table.off), ptr(table.tok), ptr(table.dst), ref.HOTWORD_N_CAP,
+        ref.HOTWORD_T_CAP, stream_ptr(logits)), "hotword_step")
+
+
 # -------------------------------------------- word timestamps (alignment)
 def _i32(t: torch.Tensor, name: str, device) -> None:
     if t.dtype != torch.int32 or not t.is_contiguous() or t.device != device:

@@ -203,6 +203,12 @@ _KERNEL_SIGS = {
                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     # (k, v, L, blocks, block_bytes, pairs, P, stream)
     "loqa_kv_copy_blocks": [c_void_p, c_void_p, c_int, c_ll, c_ll, c_void_p, c_int, c_void_p],
+    # (logits, is_bf16, ld, B, V, ctl, row_slot, hw_state, last_tok, slots, hdr, off, tok, dst,
+    #  n_cap, t_cap, stream)
+    "loqa_hotword_step": [c_void_p, c_int, c_ll, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                          c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                          c_void_p],
+    "loqa_hotword_wg": [],
 }
 
 # (argtypes, restype) of the custom all-reduce entry points (in the kernels library)

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from ..config import AUDIO_SAMPLE_RATES as RESAMPLE_RATES
+from ..config import HOTWORD_MAX_PHRASES, HOTWORD_MAX_TOKENS  # noqa: F401
 
 
 def rmsnorm(x, w, eps, residual=None):
@@ -1471,3 +1472,62 @@ def dtw(x, return_cost: bool = False, literal: bool = False):
         else:
             j -= 1
     return (tok_frame, cost[N, M]) if return_cost else tok_frame
+
+
+# ------------------------------------------------------------ hotword biasing
+# Limits of a hotword automaton (engine/hotwords.py) and the sizes its device
+# buffers are allocated at: every phrase has two token variants of at most
+# HOTWORD_MAX_TOKENS tokens, so the trie has at most HOTWORD_N_CAP nodes; the
+# flattened table (a span per node: the edges of its whole failure chain) is
+# bounded by HOTWORD_T_CAP entries, beyond which compiling raises.
+HOTWORD_N_CAP = 1 + 2 * HOTWORD_MAX_PHRASES * HOTWORD_MAX_TOKENS
+HOTWORD_T_CAP = 1 << 18
+
+
+def hotword_advance(auto, n: int, t: int) -> int:
+    """The node after ``t`` is sampled in node ``n``: the first ``m`` of
+    ``chain(n)`` = n, fail[n], ..., 0 with an edge on ``t`` gives its target;
+    none: the root."""
+    for m in auto.chain(n):
+        c = auto.edges[m].get(int(t))
+        if c is not None:
+            return c
+    return 0
+
+
+def hotword_boosted(auto, n: int) -> set:
+    """The columns that get the boost in node ``n``: the edge tokens of every
+    node of ``chain(n)``, each once however many chain nodes carry it."""
+    out = set()
+    for m in auto.chain(n):
+        out.update(auto.edges[m])
+    return out
+
+
+def hotword_step(logits, V: int, hw_ctl, row_slot, hw_state, last_tok, auto) -> None:
+    """One decoder step of hotword biasing, in place, by walking the failure
+    chains. Row b with ``hw_ctl[b]`` 1 starts at the root, with 2 at
+    ``advance(hw_state[s], last_tok[s])`` (s = ``row_slot[b]``; a state outside
+    the automaton counts as the root); the node is stored in ``hw_state[s]`` and
+    ``boost`` is added, in f32 and rounded to the logits' type (a NaN keeps its
+    bits), to every column of ``boosted(node)`` below ``V``. Any other ``hw_ctl``, or a slot out of
+    range, leaves row and state alone; so does an automaton without edges."""
+    if auto is None or auto.T == 0:
+        return
+    boost = torch.tensor(auto.boost, dtype=torch.float32)
+    slots = min(hw_state.numel(), last_tok.numel())
+    for b in range(logits.shape[0]):
+        ctl = int(hw_ctl[b])
+        s = int(row_slot[b])
+        if ctl not in (1, 2) or not 0 <= s < slots:
+            continue
+        n = 0
+        if ctl == 2:
+            n = int(hw_state[s])
+            n = hotword_advance(auto, n if 0 <= n < auto.N else 0, int(last_tok[s]))
+        hw_state[s] = n
+        cols = sorted(c for c in hotword_boosted(auto, n) if c < V)
+        if cols:
+            idx = torch.tensor(cols, dtype=torch.long)
+            x = logits[b, idx]
+            logits[b, idx] = torch.where(torch.isnan(x), x, (x.float() + boost).to(logits.dtype))

@@ -161,7 +161,10 @@ async def _build_worker_processor(spec: dict, device: str):
     tts = build_tts(cfg, device)
     # engines first (minutes of warm-up for the large models), then the bus:
     # an idle connection is not left unanswered while the loop is blocked
-    proc = build_gpu_processor(cfg, None, device, tts, skills=skills)
+    # the STT hotword list the hub's composition root resolved (no key: an
+    # older spec, resolved here from what this worker's skills loaded)
+    proc = build_gpu_processor(cfg, None, device, tts, skills=skills,
+                               hotwords=spec.get("hotwords"))
     nats = None
     if spec.get("nats_url"):
         nats = NATSService(spec["nats_url"], cfg.nats.reconnect_wait)

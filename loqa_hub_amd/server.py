@@ -91,13 +91,31 @@ def build_bridge(skills_manager=None, tts=None, fallback_parser=None):
                                      AsyncExecutionPipeline(adapter))
 
 
+def resolve_hotwords(cfg: Config, skills=None) -> list:
+    """The STT hotword list of this hub, resolved once by the composition root
+    and handed to every STT engine it builds: ``HUB_STT_HOTWORDS`` and the
+    hotword file, plus (``HUB_STT_HOTWORDS_SKILLS=on``) the ``keywords`` of every
+    skill manifest the ``SkillManager`` ``skills`` has loaded (so the root loads
+    the skills first, ``HubServer.load_skills``). A non-empty list is held to
+    the limits that need the STT tokenizer; ``ConfigError`` names the phrase."""
+    manifests = []
+    if cfg.gpu.stt_hotwords_skills == "on" and skills is not None:
+        manifests = [s.info.manifest for s in skills.skills.values()]
+    words = cfg.gpu.resolve_hotwords(manifests)
+    if words:
+        cfg.gpu.check_hotwords(words)
+    return words
+
+
 def build_gpu_processor(cfg: Config, nats, device: str = "cuda:0", tts=None, *, skills=None,
-                        llm=None, bridge: bool = True):
+                        llm=None, bridge: bool = True, hotwords=None):
     """On-device STT -> constrained intent decode -> queue (one GPU), the
     bridge on that decode, and the reply voice (``tts``: "auto" builds it from
     ``HUB_TTS_BACKEND``). ``llm``: a prebuilt engine (the tensor-parallel
     leader, ``parallel/tp_serving.py``). Speech is progressive (phrases from
-    the live decode) when ``STREAMING_ENABLED``."""
+    the live decode) when ``STREAMING_ENABLED``. ``hotwords``: the STT hotword
+    list the composition root resolved (None: ``resolve_hotwords(cfg, skills)``
+    over what ``skills`` has loaded by now)."""
     from .engine.llm_engine import LLMEngine
     from .engine.pipeline import VoicePipeline
     from .engine.stt_engine import STTEngine
@@ -122,7 +140,9 @@ def build_gpu_processor(cfg: Config, nats, device: str = "cuda:0", tts=None, *, 
                     temperatures=tuple(g.stt_temperature),
                     compression_ratio_threshold=g.stt_compression_ratio_threshold,
                     word_timestamps=g.stt_word_timestamps == "on",
-                    alignment_heads=g.stt_alignment_heads or None, beam_size=g.stt_beam_size)
+                    alignment_heads=g.stt_alignment_heads or None, beam_size=g.stt_beam_size,
+                    hotwords=resolve_hotwords(cfg, skills) if hotwords is None else hotwords,
+                    hotword_boost=g.stt_hotword_boost)
     if llm is None:
         llm = LLMEngine(lcfg, device, seed=g.seed, max_seqs=g.max_batch, weights=lw,
                         max_seq_len=g.max_seq_len, block_size=g.kv_block, use_graphs=g.use_graphs,
@@ -158,16 +178,20 @@ def build_gpu_processor(cfg: Config, nats, device: str = "cuda:0", tts=None, *, 
 
 async def build_dp_processor(cfg: Config, n_gpus: int, nats_url: str = "", *,
                              device: str = "cuda", skills_dir: str = "./skills",
-                             skills_config_store: str = "./data/skills", **spec_kw):
+                             skills_config_store: str = "./data/skills", hotwords=None,
+                             **spec_kw):
     """One worker process per GPU behind the least-loaded router (D1). Each
     worker builds the full per-GPU composition (``build_gpu_processor``: STT,
     constrained decode, command queue over its own connection to the hub's
     NATS broker at ``nats_url``, bridge, reply voice, progressive speech).
     ``device``: "cuda" (worker r on cuda:r), "cuda:0" (every worker on one
-    GPU: the shared-GPU rehearsal) or "cpu"."""
+    GPU: the shared-GPU rehearsal) or "cpu". ``hotwords``: the resolved STT
+    hotword list; it travels in the worker spec, so every worker's engine gets
+    the list the root resolved (None: the configured phrases alone)."""
     from .parallel.dp_serving import DPVoiceProcessor
     spec = {"device": device, "cfg": cfg, "nats_url": nats_url, "seed": cfg.gpu.seed,
-            "skills_dir": skills_dir, "skills_config_store": skills_config_store, **spec_kw}
+            "skills_dir": skills_dir, "skills_config_store": skills_config_store,
+            "hotwords": list(resolve_hotwords(cfg) if hotwords is None else hotwords), **spec_kw}
     dp = DPVoiceProcessor(spec, n_gpus)
     await dp.start()
     return dp
@@ -203,6 +227,7 @@ class HubServer:
         self.grpc_port = 0
         self._embedded_broker = None
         self.transcript_hints = transcript_hints     # synthetic load only (AudioService)
+        self._skills_loaded = False
 
     # ------------------------------------------------------------------ wiring
     def app(self) -> web.Application:
@@ -250,14 +275,23 @@ class HubServer:
             if hasattr(self.processor, "progressive"):
                 self.processor.progressive = False
 
+    async def load_skills(self) -> None:
+        """Register the builtin skills and load ``skills_dir`` (once; ``start``
+        calls it, and so does the composition root before it builds the
+        processor when the skill manifests feed the STT hotwords)."""
+        if self._skills_loaded:
+            return
+        self._skills_loaded = True
+        await self.skills.register_plugin(LightsSkill())
+        await self.skills.start()
+
     async def start(self, host: str | None = None, http_port: int | None = None,
                     grpc_port: int | None = None) -> None:
         import grpc
 
         from .transport.audio_proto import add_audio_service
         await self._connect_nats()
-        await self.skills.register_plugin(LightsSkill())
-        await self.skills.start()
+        await self.load_skills()
         publisher = AudioStreamPublisher(self.nats.conn) if self.nats and self.nats.conn else None
         if hasattr(self.processor, "attach_publisher"):
             self.processor.attach_publisher(publisher)   # progressive per-phrase speech

@@ -91,6 +91,8 @@ class GPUVoiceProcessor:
                       "bridge_fallback": 0, "interrupted": 0, "stt_low_confidence": 0,
                       "stt_no_speech": 0, "stt_fallback": 0,
                       "progressive": 0, "first_audio_ms_sum": 0.0, "first_audio_n": 0}
+        if getattr(getattr(pipeline, "stt", None), "hotwords_on", False):
+            self.stats["stt_hotword"] = 0   # utterances whose transcript contains a hotword
         # a list that collects every finished PipelineJob (phase timestamps for
         # a benchmark's per-phase breakdown); None: not collected
         self.job_sink: list | None = None
@@ -201,6 +203,10 @@ class GPUVoiceProcessor:
             if tr.temperature is not None:       # the engine decodes with temperature fallback
                 r.metrics["stt"].update(temperature=tr.temperature,
                                         compression_ratio=tr.compression_ratio)
+            if tr.hotwords is not None:          # the engine biases towards hotwords
+                r.metrics["stt"]["hotwords"] = list(tr.hotwords)
+                if tr.hotwords and "stt_hotword" in self.stats:
+                    self.stats["stt_hotword"] += 1
             if getattr(j, "stt_fallback", False):   # some window was decoded again
                 self.stats["stt_fallback"] += 1
             if j.no_speech:                      # dropped by the no-speech rule: no LLM pass
