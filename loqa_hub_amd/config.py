@@ -24,6 +24,8 @@ from dataclasses import dataclass, field
 # relay may record at (HUB_AUDIO_INPUT_RATE=relay) and a reply may be played at
 # (HUB_TTS_SAMPLE_RATE)
 AUDIO_SAMPLE_RATES = (8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000)
+# the frame sizes (samples) the FLAC encoder of the gpu voice offers (HUB_TTS_FLAC_BLOCK)
+FLAC_BLOCK_SIZES = (256, 512, 1024, 2048, 4096)
 
 # limits of the STT hotword list (engine/hotwords.py): phrases, and tokens per
 # token variant of a phrase. ``validate`` holds the list to the first; the
@@ -288,9 +290,13 @@ class GPUConfig:
     stt_checkpoint: str = ""          # safetensors file/dir (HF naming); "" = seeded random init
     llm_checkpoint: str = ""
     tts_checkpoint: str = ""          # HF VITS / MMS-TTS dir; "" = the random-init HUB_TTS_MODEL
-    # what a TTS_FORMAT the GPU voice cannot encode (mp3, opus, aac, flac) gets:
-    # "wav" = WAV, labelled wav, logged + counted; "error" = the synthesis fails
+    # what a TTS_FORMAT the GPU voice cannot encode (mp3, opus, aac) gets:
+    # "wav" = WAV, labelled wav, logged + counted; "error" = the synthesis fails.
+    # wav, pcm and flac are encoded (flac on the device, csrc/kernels/flac.hip)
     tts_format_policy: str = "wav"
+    # samples per frame of a flac reply, one of FLAC_BLOCK_SIZES (docs/PERF.md
+    # "FLAC replies" has the measurement behind the default)
+    tts_flac_block: int = 4096
     # tokenizer.json of a checkpoint ("": the one in / beside the checkpoint;
     # no checkpoint: the synthetic tokenizer of the random-init weights)
     stt_tokenizer: str = ""
@@ -440,6 +446,10 @@ class Config:
             raise ConfigError("invalid HUB_TTS_SAMPLE_RATE (0 | "
                               f"{' | '.join(map(str, AUDIO_SAMPLE_RATES))}): "
                               f"{self.gpu.tts_sample_rate}")
+        if self.gpu.tts_flac_block not in FLAC_BLOCK_SIZES:
+            raise ConfigError("invalid HUB_TTS_FLAC_BLOCK ("
+                              f"{' | '.join(map(str, FLAC_BLOCK_SIZES))}): "
+                              f"{self.gpu.tts_flac_block}")
         if not 0.0 <= self.gpu.stt_confirm_below <= 1.0:
             raise ConfigError("HUB_STT_CONFIRM_BELOW must be in [0, 1]: "
                               f"{self.gpu.stt_confirm_below}")
@@ -547,6 +557,16 @@ def _tts_sample_rate(e) -> int:
         return int(v)
     except ValueError:
         raise ConfigError(f"invalid configuration: invalid HUB_TTS_SAMPLE_RATE: {v}") from None
+
+
+def _tts_flac_block(e) -> int:
+    """``HUB_TTS_FLAC_BLOCK``: an integer, checked against FLAC_BLOCK_SIZES by
+    ``Config.validate``."""
+    v = env_str(e, "4096", "HUB_TTS_FLAC_BLOCK").strip()
+    try:
+        return int(v)
+    except ValueError:
+        raise ConfigError(f"invalid configuration: invalid HUB_TTS_FLAC_BLOCK: {v}") from None
 
 
 def _stt_language(e) -> str:
@@ -727,6 +747,7 @@ def load(env=None) -> Config:
             llm_checkpoint=env_str(e, "", "HUB_LLM_CHECKPOINT"),
             tts_checkpoint=env_str(e, "", "HUB_TTS_CHECKPOINT"),
             tts_format_policy=env_str(e, "wav", "HUB_TTS_FORMAT_POLICY"),
+            tts_flac_block=_tts_flac_block(e),
             stt_tokenizer=env_str(e, "", "HUB_STT_TOKENIZER"),
             llm_tokenizer=env_str(e, "", "HUB_LLM_TOKENIZER"),
         ),

@@ -3,18 +3,26 @@
 
 Concurrent ``synthesize`` calls (the progressive pipeline's phrase workers of
 every live session) are micro-batched into one padded VITS forward; each
-result is returned as a WAV (PCM16 mono, the voice's sample rate) or raw PCM.
-``speed`` maps to the duration length scale (1 / speed), as in the reference's
+result is returned as a WAV (PCM16 mono, the voice's sample rate), raw PCM or
+FLAC. ``speed`` maps to the duration length scale (1 / speed), as in the reference's
 request body.
 
 ``response_format`` (``openai_tts_client.go:39-46``; the status manager asks
-for ``mp3``, ``status_manager.go:441-462``): ``wav`` and ``pcm`` are produced
-as asked. No compressed-audio encoder ships in this image, so ``mp3``,
-``opus``, ``aac`` and ``flac`` follow ``format_policy``: ``"wav"`` (default)
-returns WAV, logs the downgrade once per format and counts it in
-``stats["format_downgrades"]``; ``"error"`` raises
-:class:`UnsupportedAudioFormat`. Either way ``TTSResult.format`` names the
-container the bytes are really in, and the hub labels the audio with it.
+for ``mp3``, ``status_manager.go:441-462``): ``wav``, ``pcm`` and ``flac`` are
+produced as asked. No lossy encoder ships in this image, so ``mp3``, ``opus``
+and ``aac`` follow ``format_policy``: ``"wav"`` (default) returns WAV, logs the
+downgrade once per format and counts it in ``stats["format_downgrades"]``;
+``"error"`` raises :class:`UnsupportedAudioFormat`. Either way
+``TTSResult.format`` names the container the bytes are really in, and the hub
+labels the audio with it.
+
+``flac`` is encoded on the device (``ops.flac_encode``, csrc/kernels/flac.hip:
+mono 16-bit FLAC, ``flac_block`` samples a frame, lossless) after the optional
+resample, on the TTS stream: the rows of a batch that asked for it leave the
+GPU as their streams' bytes - the host copies the streams' lengths, then the
+used prefix of those rows - and their PCM is never copied. The decoded reply is
+the ``pcm`` reply bit for bit. A batch with no ``flac`` row runs exactly the
+launches and copies it ran before.
 """
 from __future__ import annotations
 
@@ -36,8 +44,8 @@ from ..utils.faults import faults
 
 log = logging.getLogger("loqa.tts")
 
-SUPPORTED_FORMATS = ("wav", "pcm")
-_CONTENT_TYPES = {"wav": "audio/wav", "pcm": "audio/pcm"}
+SUPPORTED_FORMATS = ("wav", "pcm", "flac")
+_CONTENT_TYPES = {"wav": "audio/wav", "pcm": "audio/pcm", "flac": "audio/flac"}
 
 
 class UnsupportedAudioFormat(ValueError):
@@ -54,7 +62,7 @@ def pcm16_to_wav(pcm: np.ndarray, sample_rate: int) -> bytes:
 class VitsTTSEngine:
     def __init__(self, cfg: VitsConfig | None, device, *, seed: int = 0, batch_window: float = 0.003,
                  max_batch: int = 32, use_graphs: bool = True, checkpoint: str | None = None,
-                 format_policy: str = "wav", sample_rate: int = 0):
+                 format_policy: str = "wav", sample_rate: int = 0, flac_block: int = 4096):
         """``checkpoint``: a Hugging Face VITS / MMS-TTS directory (config.json,
         safetensors, vocab.json; models/loader.py ``load_vits``) — its config
         and vocabulary replace ``cfg`` and the character table; None: the
@@ -63,10 +71,14 @@ class VitsTTSEngine:
         ``sample_rate``: the rate of the returned audio (``HUB_TTS_SAMPLE_RATE``);
         0 or the voice's own rate: the voice's PCM as it is, else that PCM
         resampled on the device (``ops.pcm16_resample``) before it is copied
-        to the host."""
+        to the host. ``flac_block``: samples per frame of a ``flac`` reply
+        (``HUB_TTS_FLAC_BLOCK``), one of ``ops.FLAC_BLOCKS``."""
         if format_policy not in ("wav", "error"):
             raise ValueError(f"format_policy must be 'wav' or 'error', not {format_policy!r}")
+        if flac_block not in ops.FLAC_BLOCKS:
+            raise ValueError(f"flac_block must be one of {ops.FLAC_BLOCKS}, not {flac_block!r}")
         self.format_policy = format_policy
+        self.flac_block = flac_block
         self._downgrade_logged: set[str] = set()
         self.device = torch.device(device)
         self.vocab = None
@@ -88,13 +100,13 @@ class VitsTTSEngine:
         self._runner: VitsGraphRunner | None = None
         self.batch_window = batch_window
         self.max_batch = max_batch
-        self._pending: list[tuple[str, float, int, asyncio.Future]] = []
+        self._pending: list[tuple[str, float, int, str, asyncio.Future]] = []
         self._flusher: asyncio.Task | None = None
         self._gpu_lock = threading.Lock()
         self._stream = None            # the placed TTS stream (utils/streams.py), created lazily
         self._seed = seed
         self.stats = {"batches": 0, "phrases": 0, "samples": 0, "gpu_s": 0.0, "launch_s": 0.0,
-                      "format_downgrades": 0}
+                      "format_downgrades": 0, "flac_phrases": 0, "d2h_bytes": 0}
 
     # ---------------------------------------------------------------- batch
     # ---------------------------------------------------------------- voices
@@ -116,10 +128,15 @@ class VitsTTSEngine:
         return 0
 
     def synthesize_batch(self, texts: list[str], speeds: list[float] | None = None,
-                         speakers: list[int] | None = None) -> list[np.ndarray]:
+                         speakers: list[int] | None = None,
+                         formats: list[str] | None = None) -> list:
         """Synchronous batched synthesis -> PCM16 arrays (``speakers``: speaker
-        ids per text, multi-speaker voices)."""
+        ids per text, multi-speaker voices). ``formats``: the container each
+        text was asked in; a ``"flac"`` row is encoded on the device and comes
+        back as its FLAC stream (bytes) in place of the array."""
         speeds = speeds or [1.0] * len(texts)
+        flac = [b for b, f in enumerate(formats or ()) if f == "flac"]
+        rest = [b for b in range(len(texts)) if b not in flac]
         ids = [text_to_ids(t, self.cfg.n_symbols, self.vocab) for t in texts]
         T = max(len(i) for i in ids)
         arr = np.zeros((len(ids), T), np.int64)
@@ -143,9 +160,30 @@ class VitsTTSEngine:
                 # one more launch on the TTS stream; the lengths stay on the device
                 pcm, n = ops.pcm16_resample(pcm, n.contiguous(), self.cfg.sample_rate,
                                             self.sample_rate)
+            enc = None
+            if flac:
+                sel = None if not rest else torch.tensor(flac, dtype=torch.int64, device=self.device)
+                enc, enc_len = ops.flac_encode(
+                    pcm if sel is None else pcm.index_select(0, sel),
+                    (n if sel is None else n.index_select(0, sel)).contiguous(),
+                    self.sample_rate, self.flac_block)
+                if rest:        # only the rows that leave as PCM are copied as PCM
+                    pcm = pcm.index_select(
+                        0, torch.tensor(rest, dtype=torch.int64, device=self.device))
             t1 = time.perf_counter()
-            pcm, n = pcm.cpu().numpy(), n.cpu().numpy()
+            copied = 0
+            if rest:
+                pcm = pcm.cpu().numpy()
+                copied += pcm.nbytes
+            n = n.cpu().numpy()
+            copied += n.nbytes
+            if enc is not None:
+                # the streams' lengths first, then the used prefix of their rows
+                enc_len = enc_len.cpu().numpy()
+                enc = enc[:, : int(enc_len.max())].cpu().numpy()
+                copied += enc_len.nbytes + enc.nbytes
             t2 = time.perf_counter()
+            self.stats["d2h_bytes"] += copied
             self.stats["gpu_s"] += t2 - t0       # launch to result on the host
             self.stats["launch_s"] += t1 - t0    # host side: launches + the frame-count sync
         self.stats["batches"] += 1
@@ -153,7 +191,13 @@ class VitsTTSEngine:
             self.stats.update({f"graph_{k}": v for k, v in self._runner.stats.items()})
         self.stats["phrases"] += len(texts)
         self.stats["samples"] += int(n.sum())
-        return [pcm[b, : int(n[b])].copy() for b in range(len(texts))]
+        self.stats["flac_phrases"] += len(flac)
+        outs: list = [None] * len(texts)
+        for r, b in enumerate(rest):
+            outs[b] = pcm[r, : int(n[b])].copy()
+        for r, b in enumerate(flac):
+            outs[b] = enc[r, : int(enc_len[r])].tobytes()
+        return outs
 
     # phrase lengths (characters) and batch sizes the warm-up synthesizes: the
     # HIP-graph buckets (batch, symbols, frames) a served reply stream hits
@@ -175,8 +219,8 @@ class VitsTTSEngine:
                 self.synthesize_batch([text] * B)
         self._seed = seed                 # the served replies' noise seeds as without warm-up
         caps = self._runner.stats["captures"] if self._runner is not None else 0
-        for k in ("batches", "phrases", "samples", "gpu_s", "launch_s"):
-            self.stats[k] = 0 if k in ("batches", "phrases", "samples") else 0.0
+        for k in ("batches", "phrases", "samples", "gpu_s", "launch_s", "d2h_bytes"):
+            self.stats[k] = 0 if k in ("batches", "phrases", "samples", "d2h_bytes") else 0.0
         self.stats["warmup_captures"] = caps
         return caps
 
@@ -219,11 +263,13 @@ class VitsTTSEngine:
         spk = self.speaker_id(options.voice if options else None)
         loop = asyncio.get_running_loop()
         fut = loop.create_future()
-        self._pending.append((text, speed, spk, fut))
+        self._pending.append((text, speed, spk, fmt, fut))
         if len(self._pending) >= self.max_batch or self._flusher is None or self._flusher.done():
             self._flusher = loop.create_task(self._flush())
         pcm = await fut
-        if fmt == "pcm":
+        if fmt == "flac":
+            data = pcm                       # the row's FLAC stream, encoded on the device
+        elif fmt == "pcm":
             data = pcm.astype("<i2").tobytes()
         else:
             data = pcm16_to_wav(pcm, self.sample_rate)
@@ -235,14 +281,14 @@ class VitsTTSEngine:
             batch, self._pending = self._pending[: self.max_batch], self._pending[self.max_batch:]
             try:
                 outs = await asyncio.get_running_loop().run_in_executor(
-                    None, self.synthesize_batch, [t for t, _, _, _ in batch],
-                    [s for _, s, _, _ in batch], [k for _, _, k, _ in batch])
+                    None, self.synthesize_batch, [b[0] for b in batch], [b[1] for b in batch],
+                    [b[2] for b in batch], [b[3] for b in batch])
             except Exception as e:  # noqa: BLE001
                 for *_, f in batch:
                     if not f.done():
                         f.set_exception(e)
                 continue
-            for (_, _, _, f), pcm in zip(batch, outs):
+            for (*_, f), pcm in zip(batch, outs):
                 if not f.done():
                     f.set_result(pcm)
 

@@ -1024,6 +1024,53 @@ def pcm16_resample(pcm: torch.Tensor, lens: torch.Tensor, rate_in: int, rate_out
     return out, n_out
 
 
+FLAC_BLOCKS = ref.FLAC_BLOCKS
+
+
+def flac_encode(pcm: torch.Tensor, lens: torch.Tensor, rate: int, block: int = 4096,
+                out: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """PCM16 rows [R, N] (inner stride 1, any row stride >= N) holding ``lens``
+    [R] samples (int32 / int64, on the device: the host never reads them;
+    clamped to [0, N]) at ``rate`` -> (uint8 [R, cap], int32 out_len [R]): row
+    b's FLAC stream is out[b, :out_len[b]], nothing is written beyond it. The
+    bytes are ``ref.flac_encode``'s (mono, 16 bits, ``block`` samples a frame,
+    CONSTANT / VERBATIM / FIXED subframes); cap = 42 + ceil(N / block) (2 block
+    + 15). ``out``: a contiguous uint8 [R, cap] to write into (GPU only). Three
+    launches (csrc/kernels/flac.hip), no host synchronisation."""
+    if pcm.dim() != 2 or pcm.dtype != torch.int16 or lens.numel() != pcm.shape[0]:
+        raise ValueError(f"flac_encode wants int16 [R, N] and R lengths, got "
+                         f"{tuple(pcm.shape)} {pcm.dtype}, {lens.numel()} lengths")
+    R, N = pcm.shape
+    frames = ref.flac_check(N, rate, block)          # before any work
+    if N > 1 and pcm.stride(1) != 1:
+        raise ValueError("flac_encode rows must be contiguous in their samples")
+    cap = ref.flac_capacity(N, block)
+    if not _gpu(pcm):
+        streams = ref.flac_encode(pcm, lens, rate, block)
+        out = torch.zeros(R, cap, dtype=torch.uint8)
+        for b, st in enumerate(streams):
+            out[b, :len(st)] = torch.frombuffer(bytearray(st), dtype=torch.uint8)
+        return out, torch.tensor([len(st) for st in streams], dtype=torch.int32)
+    ld = pcm.stride(0) if R > 1 else N           # a single row's stride means nothing
+    if ld < N:
+        raise ValueError(f"flac_encode row stride {ld} < {N} samples")
+    assert lens.dtype in (torch.int32, torch.int64) and lens.is_contiguous() and lens.is_cuda
+    dev = pcm.device
+    if out is None:
+        out = torch.empty(R, cap, dtype=torch.uint8, device=dev)
+    elif out.shape != (R, cap) or out.dtype != torch.uint8 or not out.is_contiguous() \
+            or out.device != dev:
+        raise ValueError(f"flac_encode out must be a contiguous uint8 [{R}, {cap}] on {dev}")
+    out_len = torch.empty(R, dtype=torch.int32, device=dev)
+    staging = torch.empty(R * frames * (2 * block + 16), dtype=torch.uint8, device=dev)
+    sizes = torch.empty(2, max(R * frames, 1), dtype=torch.int32, device=dev)   # sizes, offsets
+    check(kernels().loqa_flac_encode(ptr(pcm), ld, N, ptr(lens), int(lens.dtype == torch.int64),
+                                     R, rate, block, ptr(out), cap, ptr(out_len), ptr(staging),
+                                     ptr(sizes[0]), ptr(sizes[1]), stream_ptr(pcm)),
+          "flac_encode")
+    return out, out_len
+
+
 def log_mel(audio: torch.Tensor, consts: "ref.MelConstants") -> torch.Tensor:
     """audio [B, n_samples] f32 (padded to 30 s) -> whisper log-mel [B, n_mels, frames] bf16."""
     if not _gpu(audio):

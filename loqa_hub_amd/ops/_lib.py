@@ -97,6 +97,10 @@ _KERNEL_SIGS = {
     # (in, ld_in, max_in, n, n_is64, out, ld_out, n_out, B, L, M, T, table, stream)
     "loqa_pcm16_resample": [c_void_p, c_ll, c_ll, c_void_p, c_int, c_void_p, c_ll, c_void_p, c_int, c_int,
                             c_int, c_int, c_void_p, c_void_p],
+    # (pcm, ld, N, lens, lens_is64, R, rate, block, out, cap, out_len, staging, sizes, offsets,
+    #  stream)
+    "loqa_flac_encode": [c_void_p, c_ll, c_ll, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                         c_ll, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "loqa_masked_argmax": [c_void_p, c_int, c_ll, c_int, c_int, c_void_p, c_void_p, c_int,
                            # (..., out_idx, workspace, token_ids, stream)
                            c_void_p, c_void_p, c_void_p, c_void_p],

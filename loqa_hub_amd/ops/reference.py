@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from ..config import AUDIO_SAMPLE_RATES as RESAMPLE_RATES
+from ..config import FLAC_BLOCK_SIZES as FLAC_BLOCKS
 from ..config import HOTWORD_MAX_PHRASES, HOTWORD_MAX_TOKENS  # noqa: F401
 
 
@@ -745,6 +746,330 @@ def pcm16_resample(pcm, lens, rate_in: int, rate_out: int):
         y = resample(x[b, :n[b]].astype(np.float64), rate_in, rate_out)
         out[b, :n_out[b]] = np.clip(np.rint(y), -32768, 32767).astype(np.int16)
     return torch.from_numpy(out), torch.from_numpy(n_out.astype(np.int32))
+
+
+# ------------------------------------------------------------------------ FLAC
+# Mono 16-bit FLAC with a fixed block size and the FIXED predictors only: the
+# model of csrc/kernels/flac.hip, which must give these bytes. Every decision is
+# integer arithmetic (docs/ARCHITECTURE.md "FLAC replies" states the rule).
+FLAC_MAX_FRAMES = 65536          # frame numbers of at most 3 coded bytes
+FLAC_HEADER_BYTES = 42           # "fLaC" + block header + STREAMINFO
+_FLAC_RATE_CODE = {8000: 4, 16000: 5, 22050: 6, 24000: 7, 32000: 8, 44100: 9, 48000: 10}
+
+
+def flac_check(n_max: int, rate: int, block: int) -> int:
+    """The checks made before any work; returns the frames of an ``n_max``-sample row."""
+    check_rate(rate)
+    if block not in FLAC_BLOCKS:
+        raise ValueError(f"FLAC block size must be one of {FLAC_BLOCKS}, not {block}")
+    if n_max < 0:
+        raise ValueError(f"negative sample count {n_max}")
+    frames = -(-int(n_max) // block)
+    if frames > FLAC_MAX_FRAMES:
+        raise ValueError(f"{frames} FLAC frames of {block} samples: more than {FLAC_MAX_FRAMES}")
+    return frames
+
+
+def flac_capacity(n_max: int, block: int) -> int:
+    """Bytes that hold any stream of ``n_max`` samples: a VERBATIM frame is at
+    most 2 n + 15 bytes (header <= 12, subframe byte, footer 2)."""
+    return FLAC_HEADER_BYTES + -(-int(n_max) // block) * (2 * block + 15)
+
+
+def _crc_table(poly: int, width: int) -> list:
+    top, mask = 1 << (width - 1), (1 << width) - 1
+    tab = []
+    for b in range(256):
+        c = b << (width - 8)
+        for _ in range(8):
+            c = ((c << 1) ^ poly) & mask if c & top else (c << 1) & mask
+        tab.append(c)
+    return tab
+
+
+_CRC8_TAB = _crc_table(0x07, 8)
+_CRC16_TAB = _crc_table(0x8005, 16)
+
+
+def _flac_crc8(data) -> int:
+    c = 0
+    for b in data:
+        c = _CRC8_TAB[c ^ b]
+    return c
+
+
+def _flac_crc16(data) -> int:
+    c = 0
+    for b in data:
+        c = ((c << 8) & 0xFFFF) ^ _CRC16_TAB[(c >> 8) ^ b]
+    return c
+
+
+def _flac_bits(values, width: int) -> np.ndarray:
+    """The low ``width`` bits of each value, MSB first, as a flat 0/1 array."""
+    v = np.atleast_1d(np.asarray(values, np.int64))
+    return ((v[:, None] >> np.arange(width - 1, -1, -1)) & 1).astype(np.uint8).ravel()
+
+
+def flac_frame_plan(x) -> tuple:
+    """The selection rule for one block of samples: ("constant",), ("verbatim",)
+    or ("fixed", order, partition order, [k per partition])."""
+    x = np.asarray(x, np.int64)
+    n = x.shape[0]
+    if (x == x[0]).all():
+        return ("constant",)
+    omax = min(4, n - 1)
+    res = [x]
+    for _ in range(omax):
+        res.append(np.diff(res[-1]))
+    # E_o over the samples every order predicts, i = omax .. n-1
+    err = [int(np.abs(res[o][omax - o:]).sum()) for o in range(omax + 1)]
+    o = int(np.argmin(err))
+    r = res[o]
+    u = np.where(r >= 0, 2 * r, -2 * r - 1)
+    pad = np.concatenate([np.zeros(o, np.int64), u])        # zeros add nothing to a sum
+    best = None
+    for p in range(9):
+        if n % (1 << p) or (n >> p) <= o:
+            continue
+        parts = pad.reshape(1 << p, n >> p)
+        cnt = np.full(1 << p, n >> p, np.int64)
+        cnt[0] -= o
+        ks = np.arange(15, dtype=np.int64)
+        cost = cnt[:, None] * (ks + 1)[None] + (parts[:, :, None] >> ks).sum(1)
+        k = cost.argmin(1)                                   # the lowest k on ties
+        bits = int((4 + cost[np.arange(1 << p), k]).sum())
+        if best is None or bits < best[0]:
+            best = (bits, p, k)
+    bits, p, k = best
+    if 16 * o + 6 + bits >= 16 * n:
+        return ("verbatim",)
+    return ("fixed", o, p, [int(v) for v in k])
+
+
+def _flac_frame(x: np.ndarray, number: int, rate: int, block: int) -> bytes:
+    n = x.shape[0]
+    hdr = bytearray(b"\xff\xf8")
+    if n == block:
+        size_code, size_extra = 8 + FLAC_BLOCKS.index(block), b""
+    elif n <= 256:
+        size_code, size_extra = 6, bytes([n - 1])
+    else:
+        size_code, size_extra = 7, (n - 1).to_bytes(2, "big")
+    rate_code = _FLAC_RATE_CODE.get(rate, 13)
+    hdr.append(size_code << 4 | rate_code)
+    hdr.append(0x08)                                         # mono, 16 bits
+    if number < 0x80:
+        hdr.append(number)
+    elif number < 0x800:
+        hdr += bytes([0xC0 | number >> 6, 0x80 | number & 0x3F])
+    else:
+        hdr += bytes([0xE0 | number >> 12, 0x80 | (number >> 6) & 0x3F, 0x80 | number & 0x3F])
+    hdr += size_extra
+    if rate_code == 13:
+        hdr += rate.to_bytes(2, "big")
+    hdr.append(_flac_crc8(hdr))
+
+    plan = flac_frame_plan(x)
+    if plan[0] == "constant":
+        bits = [_flac_bits(0, 8), _flac_bits(x[0], 16)]
+    elif plan[0] == "verbatim":
+        bits = [_flac_bits(1 << 1, 8), _flac_bits(x, 16)]
+    else:
+        _, o, p, ks = plan
+        r = np.diff(x, o) if o else x
+        u = np.where(r >= 0, 2 * r, -2 * r - 1)
+        bits = [_flac_bits((8 | o) << 1, 8), _flac_bits(x[:o], 16), _flac_bits(p, 6)]
+        first = 0
+        for j, k in enumerate(ks):
+            cnt = (n >> p) - (o if j == 0 else 0)
+            v = u[first:first + cnt]
+            first += cnt
+            q = v >> k
+            end = np.cumsum(q + 1 + k)
+            code = np.zeros(int(end[-1]) if cnt else 0, np.uint8)
+            one = end - k - 1
+            code[one] = 1
+            for b in range(k):
+                code[one + 1 + b] = (v >> (k - 1 - b)) & 1
+            bits += [_flac_bits(k, 4), code]
+    body = np.concatenate(bits)
+    body = np.packbits(np.concatenate([body, np.zeros(-body.shape[0] % 8, np.uint8)])).tobytes()
+    frame = bytes(hdr) + body
+    return frame + _flac_crc16(frame).to_bytes(2, "big")
+
+
+def flac_encode(pcm_rows, lens, rate: int, block: int = 4096) -> list:
+    """int16 rows [R, N] holding ``lens`` [R] samples (clamped to [0, N]) at
+    ``rate`` -> one FLAC stream (bytes) per row: mono, 16 bits, ``block``
+    samples per frame, CONSTANT / VERBATIM / FIXED subframes by the rule of
+    ``flac_frame_plan``. The CPU path of ``ops.flac_encode`` and the arbiter of
+    its kernel."""
+    x = pcm_rows.cpu().numpy() if isinstance(pcm_rows, torch.Tensor) else np.asarray(pcm_rows)
+    assert x.ndim == 2 and x.dtype == np.int16
+    flac_check(x.shape[1], rate, block)
+    n_all = np.clip(np.asarray(lens.cpu() if isinstance(lens, torch.Tensor) else lens, np.int64),
+                    0, x.shape[1])
+    out = []
+    for row, n in zip(x, n_all):
+        n = int(n)
+        frames = [_flac_frame(row[f:min(f + block, n)].astype(np.int64), f // block, rate, block)
+                  for f in range(0, n, block)]
+        sizes = [len(f) for f in frames]
+        info = (block.to_bytes(2, "big") * 2 + (min(sizes) if sizes else 0).to_bytes(3, "big")
+                + (max(sizes) if sizes else 0).to_bytes(3, "big")
+                + (rate << 44 | 0 << 41 | 15 << 36 | n).to_bytes(8, "big") + bytes(16))
+        out.append(b"fLaC\x80\x00\x00\x22" + info + b"".join(frames))
+    return out
+
+
+def flac_info(data: bytes) -> tuple:
+    """(sample_rate, n_samples) of a FLAC stream, read from STREAMINFO."""
+    if data[:4] != b"fLaC" or data[4] & 0x7F != 0:
+        raise ValueError("not a FLAC stream that starts with STREAMINFO")
+    v = int.from_bytes(data[18:26], "big")
+    return v >> 44, v & ((1 << 36) - 1)
+
+
+class _FlacReader:
+    """MSB-first bit reader of the decoder."""
+
+    def __init__(self, data: bytes, pos: int):
+        self.data, self.pos = data, pos * 8
+
+    def read(self, width: int) -> int:
+        if self.pos + width > len(self.data) * 8:
+            raise ValueError("FLAC stream ends inside a frame")
+        a, b = self.pos >> 3, (self.pos + width + 7) >> 3
+        v = int.from_bytes(self.data[a:b], "big") >> (b * 8 - self.pos - width)
+        self.pos += width
+        return v & ((1 << width) - 1)
+
+    def signed(self, width: int) -> int:
+        v = self.read(width)
+        return v - (1 << width) if v >> (width - 1) else v
+
+    def unary(self) -> int:
+        q = 0
+        while True:                       # whole zero bytes first, then bit by bit
+            if self.pos & 7 == 0 and self.pos >> 3 < len(self.data) and not self.data[self.pos >> 3]:
+                q, self.pos = q + 8, self.pos + 8
+            elif self.read(1):
+                return q
+            else:
+                q += 1
+
+
+def flac_decode(data: bytes) -> tuple:
+    """FLAC stream -> (int16 [channels, n], sample_rate). Its own code, none of
+    the encoder's: it checks each frame's CRC-8 and CRC-16, that the frame
+    numbers count 0, 1, 2, ... and that the stream ends with its last frame.
+    It reads what ``flac_encode`` writes (fixed block size, CONSTANT / VERBATIM /
+    FIXED subframes, 4-bit Rice parameters) and also wasted bits and two
+    independent channels."""
+    rate_info, total = flac_info(data)
+    if data[4] != 0x80 or int.from_bytes(data[5:8], "big") != 34:
+        raise ValueError("FLAC metadata other than one STREAMINFO block")
+    info_bits = (int.from_bytes(data[18:26], "big") >> 36) & 0xFF
+    channels_info, bps_info = (info_bits >> 5) + 1, (info_bits & 31) + 1
+    rates = {4: 8000, 5: 16000, 6: 22050, 7: 24000, 8: 32000, 9: 44100, 10: 48000}
+    sizes = {1: 8, 2: 12, 4: 16, 5: 20, 6: 24}
+    chans: list = [[] for _ in range(channels_info)]
+    pos, expect = FLAC_HEADER_BYTES, 0
+    while pos < len(data):
+        rd = _FlacReader(data, pos)
+        if rd.read(15) != 0x7FFC:
+            raise ValueError(f"no frame sync at byte {pos}")
+        if rd.read(1):
+            raise ValueError("variable block size streams are not supported")
+        size_code, rate_code = rd.read(4), rd.read(4)
+        assign, bps_code, reserved = rd.read(4), rd.read(3), rd.read(1)
+        if reserved or assign not in (0, 1) or assign + 1 != channels_info:
+            raise ValueError(f"channel assignment {assign} not supported")
+        lead = rd.read(8)                                  # the coded frame number
+        extra = 0 if lead < 0x80 else 1 if lead >> 5 == 6 else 2 if lead >> 4 == 14 else None
+        if extra is None:
+            raise ValueError("frame number longer than 3 bytes")
+        number = lead if not extra else lead & (0x1F >> (extra - 1))
+        for _ in range(extra):
+            cont = rd.read(8)
+            if cont >> 6 != 2:
+                raise ValueError("bad frame number continuation byte")
+            number = number << 6 | cont & 0x3F
+        if number != expect:
+            raise ValueError(f"frame number {number}, expected {expect}")
+        expect += 1
+        if size_code == 6:
+            n = rd.read(8) + 1
+        elif size_code == 7:
+            n = rd.read(16) + 1
+        elif size_code >= 8:
+            n = 256 << (size_code - 8)
+        else:
+            raise ValueError(f"block size code {size_code} not supported")
+        rate = rd.read(16) if rate_code == 13 else rate_info if rate_code == 0 else rates[rate_code]
+        if rate != rate_info:
+            raise ValueError("frame sample rate differs from STREAMINFO")
+        bps = bps_info if bps_code == 0 else sizes[bps_code]
+        head_end = rd.pos >> 3
+        crc = 0
+        for byte in data[pos:head_end]:                    # bitwise, unlike the encoder's table
+            crc ^= byte
+            for _ in range(8):
+                crc = (crc << 1 ^ 0x07) & 0xFF if crc & 0x80 else crc << 1
+        if crc != rd.read(8):
+            raise ValueError(f"CRC-8 mismatch in frame {number}")
+        for ch in range(channels_info):
+            if rd.read(1):
+                raise ValueError("subframe padding bit set")
+            kind, wasted = rd.read(6), rd.read(1)
+            if wasted:
+                wasted = rd.unary() + 1
+            width = bps - wasted
+            if kind == 0:
+                s = np.full(n, rd.signed(width), np.int64)
+            elif kind == 1:
+                s = np.array([rd.signed(width) for _ in range(n)], np.int64)
+            elif 8 <= kind <= 12:
+                o = kind - 8
+                warm = np.array([rd.signed(width) for _ in range(o)], np.int64)
+                if rd.read(2) != 0:
+                    raise ValueError("only 4-bit Rice parameters are supported")
+                p = rd.read(4)
+                if n % (1 << p) or (n >> p) < o:
+                    raise ValueError("partition order does not fit the block")
+                r = []
+                for j in range(1 << p):
+                    k = rd.read(4)
+                    if k == 15:
+                        raise ValueError("escaped partitions are not supported")
+                    for _ in range((n >> p) - (o if j == 0 else 0)):
+                        v = rd.unary() << k | (rd.read(k) if k else 0)
+                        r.append(-(v >> 1) - 1 if v & 1 else v >> 1)
+                s = np.asarray(r, np.int64)
+                for j in range(o - 1, -1, -1):              # undo one difference per pass
+                    start = np.diff(warm, j)[-1] if j else warm[-1]
+                    s = start + np.cumsum(s)
+                s = np.concatenate([warm, s])
+            else:
+                raise ValueError(f"subframe type {kind} not supported")
+            chans[ch].append(s << wasted)
+        rd.pos = (rd.pos + 7) & ~7
+        end = rd.pos >> 3
+        crc = 0
+        for byte in data[pos:end]:
+            crc ^= byte << 8
+            for _ in range(8):
+                crc = (crc << 1 ^ 0x8005) & 0xFFFF if crc & 0x8000 else crc << 1
+        if crc != rd.read(16):
+            raise ValueError(f"CRC-16 mismatch in frame {number}")
+        pos = end + 2
+    out = np.stack([np.concatenate(c) if c else np.zeros(0, np.int64) for c in chans])
+    if out.shape[1] != total:
+        raise ValueError(f"{out.shape[1]} samples decoded, STREAMINFO says {total}")
+    if out.size and (out.min() < -32768 or out.max() > 32767):
+        raise ValueError("decoded sample outside 16 bits")
+    return out.astype(np.int16), rate_info
 
 
 # ------------------------------------------------------------- log-mel consts

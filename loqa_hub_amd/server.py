@@ -59,7 +59,8 @@ def build_tts(cfg: Config, device: str = "cuda:0"):
         return VitsTTSEngine(None if ckpt else vits_config(cfg.gpu.tts_model), device,
                              seed=cfg.gpu.seed, batch_window=win, checkpoint=ckpt,
                              format_policy=cfg.gpu.tts_format_policy,
-                             sample_rate=cfg.gpu.tts_sample_rate)
+                             sample_rate=cfg.gpu.tts_sample_rate,
+                             flac_block=cfg.gpu.tts_flac_block)
     if b in ("http", "openai"):
         from .llm.tts import OpenAITTSClient
         return OpenAITTSClient(cfg.tts)

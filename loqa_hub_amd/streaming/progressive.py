@@ -115,6 +115,20 @@ def wav_pcm(data: bytes) -> tuple[int, bytes] | None:
             f.seek(n, 1)
 
 
+def phrase_audio_info(audio: bytes, content_type: str) -> tuple[str, int, int]:
+    """(format label, sample rate, samples) of one phrase's audio: read from the
+    bytes for WAV and FLAC; any other container is labelled by its content type
+    and says nothing of its rate (0, 0)."""
+    w = wav_pcm(audio)
+    if w:
+        return "wav", w[0], len(w[1]) // 2
+    fmt = content_type.split("/")[-1] or "wav"
+    if fmt == "flac":
+        from ..ops.reference import flac_info
+        return (fmt, *flac_info(audio))
+    return fmt, 0, 0
+
+
 _session_ids = itertools.count(1)
 
 
@@ -137,6 +151,8 @@ class ProgressiveSpeech:
         self.pc = pipeline.start_pipeline(self.session_id, self.phrases)
         self.chunks: list = []
         self.published = 0
+        # what the phrases are (the label, rate and samples of the reply so far)
+        self.format, self.sample_rate, self.samples = "wav", 0, 0
         self.t_start = time.perf_counter()
         self.mono_start = time.monotonic()   # the streaming metrics' clock
         self.t_first_piece = 0.0       # first character of the reply field
@@ -206,13 +222,13 @@ class ProgressiveSpeech:
                 if chunk.is_last or self.interrupted:
                     break
                 self.chunks.append(chunk)
+                fmt, sr, ns = phrase_audio_info(chunk.audio, chunk.content_type)
+                self.format, self.sample_rate, self.samples = fmt, sr, self.samples + ns
                 if self.publisher is not None:
-                    w = wav_pcm(chunk.audio)
-                    sr = w[0] if w else 22050
-                    fmt = "wav" if w else (chunk.content_type.split("/")[-1] or "wav")
                     try:
-                        await self.publisher.stream_audio_to_relay(self.relay_id, chunk.audio, fmt, sr,
-                                                                   "response", 3)
+                        # a container that does not carry its rate: the reference's guess
+                        await self.publisher.stream_audio_to_relay(self.relay_id, chunk.audio, fmt,
+                                                                   sr or 22050, "response", 3)
                         self.published += 1
                     except Exception as e:  # noqa: BLE001
                         log.warning("phrase publish to %s failed: %s", self.relay_id, e)
@@ -227,7 +243,10 @@ class ProgressiveSpeech:
     async def finish(self, fallback_text: str = "") -> tuple[bytes, int]:
         """After the decode: speak ``fallback_text`` if the reply field never
         streamed (e.g. a parse fallback), wait for every phrase, and return
-        the whole reply as one WAV (sample rate) for the gRPC response."""
+        the whole reply as one WAV (sample rate) for the gRPC response. Phrases
+        in another container (``self.format``: flac, ...) cannot be joined into
+        one file: then no audio is returned, only the phrases' rate
+        (``self.samples`` counts what they hold)."""
         if not self._closed:
             rest = self.pb.flush()
             if rest:
@@ -240,7 +259,7 @@ class ProgressiveSpeech:
         for c in self.chunks:
             w = wav_pcm(c.audio)
             if w is None:
-                return (self.chunks[-1].audio if self.chunks else b""), 0
+                return b"", self.sample_rate
             sr = w[0]
             pcm.append(w[1])
         if not pcm:

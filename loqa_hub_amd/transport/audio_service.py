@@ -401,7 +401,11 @@ class AudioService:
         if self.audio_publisher is None:
             log.warning("NATS audio publisher not available, skipping response to relay %s", relay_id)
             return
-        sr = res.audio_sample_rate or (22050 if res.audio_format == "mp3" else 16000)
+        sr = res.audio_sample_rate
+        if not sr and res.audio_format == "flac":
+            from ..ops.reference import flac_info      # a FLAC stream states its rate
+            sr = flac_info(res.audio)[0]
+        sr = sr or (22050 if res.audio_format == "mp3" else 16000)
         try:
             await self.audio_publisher.stream_audio_to_relay(
                 relay_id, res.audio, res.audio_format, sr,

@@ -64,6 +64,13 @@ def _result_from(text: str, mc: MultiCommand | None, queue_ok: bool | None,
     return res
 
 
+def _flac_rate_duration(data: bytes) -> tuple[int, float]:
+    """(sample rate, seconds) of a FLAC reply, from its STREAMINFO."""
+    from ..ops.reference import flac_info
+    rate, n = flac_info(data)
+    return rate, n / rate if rate else 0.0
+
+
 class GPUVoiceProcessor:
     takes_pcm16 = True      # AudioService hands over the relay's raw PCM16 samples
 
@@ -220,10 +227,17 @@ class GPUVoiceProcessor:
             await self._bridge(r, j, ack=speech is None)
         if speech is not None:
             audio_b, sr = await self._end_speech(relay_id, speech, r.response_text)
-            r.audio, r.audio_format, r.audio_sample_rate = audio_b, "wav", sr
+            r.audio, r.audio_format, r.audio_sample_rate = audio_b, speech.format, sr
             r.audio_published = self.publisher is not None and speech.published > 0
-            if sr:
-                r.audio_duration = max(0, len(audio_b) - 44) / 2 / sr
+            if speech.format == "wav":
+                if sr:
+                    r.audio_duration = max(0, len(audio_b) - 44) / 2 / sr
+            elif not r.audio_published:
+                # phrases that are not WAV do not join into one file, and nobody
+                # received them: the reply is synthesised once, as a whole
+                await self._speak([r])
+            elif sr:
+                r.audio_duration = speech.samples / sr
             m = speech.metrics()
             done_t = j.t.get("llm_done", 0.0)
             m["first_phrase_before_decode_done"] = bool(speech.t_first_phrase and done_t
@@ -288,6 +302,8 @@ class GPUVoiceProcessor:
                 if t.sample_rate:
                     r.audio_sample_rate = t.sample_rate
                     r.audio_duration = len(t.audio) / 2 / t.sample_rate
+                if r.audio_format == "flac":
+                    r.audio_sample_rate, r.audio_duration = _flac_rate_duration(t.audio)
             except Exception as e:  # noqa: BLE001
                 log.warning("TTS failed: %s", e)
         await asyncio.gather(*[one(r) for r in results])
@@ -352,5 +368,7 @@ class ServiceVoiceProcessor:
         try:
             t = await self.tts.synthesize(r.response_text, TTSOptions(response_format=self.tts_format))
             r.audio, r.audio_format = t.audio, t.format or self.tts_format
+            if r.audio_format == "flac":     # a FLAC reply always carries its own rate
+                r.audio_sample_rate, r.audio_duration = _flac_rate_duration(t.audio)
         except Exception as e:  # noqa: BLE001
             log.warning("TTS failed: %s", e)
