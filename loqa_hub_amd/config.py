@@ -34,6 +34,12 @@ FLAC_BLOCK_SIZES = (256, 512, 1024, 2048, 4096)
 HOTWORD_MAX_PHRASES = 1024
 HOTWORD_MAX_TOKENS = 16
 
+# VadConfig field -> the knob that sets it (Config.validate names the knob)
+_VAD_KEYS = {"threshold_db": "HUB_VAD_THRESHOLD_DB", "min_level_dbfs": "HUB_VAD_MIN_LEVEL_DBFS",
+             "floor_max_dbfs": "HUB_VAD_FLOOR_MAX_DBFS", "floor_s": "HUB_VAD_FLOOR_S",
+             "min_speech_ms": "HUB_VAD_MIN_SPEECH_MS", "min_silence_ms": "HUB_VAD_MIN_SILENCE_MS",
+             "pad_ms": "HUB_VAD_PAD_MS"}
+
 _DUR_RE = re.compile(r"([0-9]*\.?[0-9]+)(ns|us|µs|ms|s|m|h)")
 _UNIT = {"ns": 1e-9, "us": 1e-6, "µs": 1e-6, "ms": 1e-3, "s": 1.0, "m": 60.0, "h": 3600.0}
 
@@ -272,6 +278,24 @@ class GPUConfig:
     stt_hotwords_file: str = ""
     stt_hotword_boost: float = 2.0
     stt_hotwords_skills: str = "off"  # off | on
+    # voice activity detection on the gpu backend, over the relay PCM the ingest
+    # path holds on the device: an utterance without speech is answered with
+    # no_speech before any encoder pass, the encoder windows start and end at
+    # speech and long audio is cut at pauses instead of fixed 30 s marks. A 20 ms
+    # frame is speech when its mean square is at least vad_min_level_dbfs and
+    # vad_threshold_db above the noise floor (the minimum within vad_floor_s on
+    # each side, at most vad_floor_max_dbfs); runs shorter than
+    # vad_min_speech_ms are dropped, gaps shorter than vad_min_silence_ms filled,
+    # vad_pad_ms added around speech (milliseconds: multiples of 20). The
+    # defaults are not tuned on speech data; they lean towards keeping audio.
+    stt_vad: str = "off"              # off | on
+    vad_threshold_db: float = 9.0
+    vad_min_level_dbfs: float = -55.0
+    vad_floor_max_dbfs: float = -30.0
+    vad_floor_s: float = 3.0
+    vad_min_speech_ms: int = 100
+    vad_min_silence_ms: int = 500
+    vad_pad_ms: int = 200
     # relay audio: "fixed" (every chunk is 16 kHz, AudioChunk.sample_rate is
     # ignored: the reference's behaviour) or "relay" (the stream's own rate, one
     # of AUDIO_SAMPLE_RATES; the gpu STT resamples it to 16 kHz on the device,
@@ -332,6 +356,17 @@ class GPUConfig:
             return load_tokenizer(explicit, vocab_size)
         ckpt = getattr(self, f"{which}_checkpoint")
         return load_tokenizer(ckpt, vocab_size) if find_tokenizer(ckpt) else None
+
+    def vad_config(self, always: bool = False):
+        """``VadConfig`` of the ``HUB_VAD_*`` knobs for ``STTEngine(vad=...)``
+        (None: ``HUB_STT_VAD=off``, unless ``always``); ValueError for a value
+        out of range."""
+        if self.stt_vad != "on" and not always:
+            return None
+        from .engine.stt_vad import VadConfig
+        return VadConfig(self.vad_threshold_db, self.vad_min_level_dbfs, self.vad_floor_max_dbfs,
+                         self.vad_floor_s, self.vad_min_speech_ms, self.vad_min_silence_ms,
+                         self.vad_pad_ms)
 
     @property
     def hotwords_on(self) -> bool:
@@ -527,6 +562,16 @@ class Config:
             if b > 1:
                 raise ConfigError("HUB_STT_BEAM_SIZE > 1 does not combine with HUB_STT_HOTWORDS "
                                   "(beams carry no hotword state)")
+        if self.gpu.stt_vad not in ("off", "on"):
+            raise ConfigError(f"invalid HUB_STT_VAD (off | on): {self.gpu.stt_vad}")
+        if self.gpu.stt_vad == "on" and self.gpu.stt_backend != "gpu":
+            raise ConfigError(f"HUB_STT_VAD=on needs HUB_STT_BACKEND=gpu: {self.gpu.stt_backend}")
+        try:
+            # the bounds live with the detector's parameters (ops.reference.vad_params)
+            self.gpu.vad_config(always=True)
+        except ValueError as e:
+            key = next((k for name, k in _VAD_KEYS.items() if f" {name} " in str(e)), "HUB_VAD_*")
+            raise ConfigError(f"invalid {key}: {e}") from None
         if not self.gpu.stt_compression_ratio_threshold > 0.0:
             raise ConfigError("HUB_STT_COMPRESSION_RATIO_THRESHOLD must be > 0: "
                               f"{self.gpu.stt_compression_ratio_threshold}")
@@ -609,6 +654,15 @@ def _beam_size(e) -> int:
         return 1
     if not re.fullmatch(r"[+-]?\d+", v):
         raise ConfigError(f"invalid configuration: invalid HUB_STT_BEAM_SIZE: {v}")
+    return int(v)
+
+
+def _strict_int(e, default: int, key: str) -> int:
+    v = env_str(e, "", key).strip()
+    if v == "":
+        return default
+    if not re.fullmatch(r"[+-]?\d+", v):
+        raise ConfigError(f"invalid configuration: invalid {key}: {v}")
     return int(v)
 
 
@@ -736,6 +790,14 @@ def load(env=None) -> Config:
             stt_hotwords_skills=env_str(e, "off", "HUB_STT_HOTWORDS_SKILLS").strip().lower(),
             stt_compression_ratio_threshold=_strict_float(e, 2.4,
                                                           "HUB_STT_COMPRESSION_RATIO_THRESHOLD"),
+            stt_vad=env_str(e, "off", "HUB_STT_VAD").strip().lower(),
+            vad_threshold_db=_strict_float(e, 9.0, "HUB_VAD_THRESHOLD_DB"),
+            vad_min_level_dbfs=_strict_float(e, -55.0, "HUB_VAD_MIN_LEVEL_DBFS"),
+            vad_floor_max_dbfs=_strict_float(e, -30.0, "HUB_VAD_FLOOR_MAX_DBFS"),
+            vad_floor_s=_strict_float(e, 3.0, "HUB_VAD_FLOOR_S"),
+            vad_min_speech_ms=_strict_int(e, 100, "HUB_VAD_MIN_SPEECH_MS"),
+            vad_min_silence_ms=_strict_int(e, 500, "HUB_VAD_MIN_SILENCE_MS"),
+            vad_pad_ms=_strict_int(e, 200, "HUB_VAD_PAD_MS"),
             audio_input_rate=env_str(e, "fixed", "HUB_AUDIO_INPUT_RATE").lower(),
             tts_sample_rate=_tts_sample_rate(e),
             tts_backend=env_str(e, "gpu", "HUB_TTS_BACKEND"),

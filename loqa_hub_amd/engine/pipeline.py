@@ -53,7 +53,11 @@ class PipelineJob:
     queue: ExecutionResult | None = None
     error: str = ""
     stt_failed: bool = False
-    no_speech: bool = False                 # every window fell to the STT engine's no-speech rule
+    # every window fell to the STT engine's no-speech rule, or its voice
+    # activity detector found no speech (``vad_silent``: the utterance was not
+    # transcribed at all)
+    no_speech: bool = False
+    vad_silent: bool = False
     stt_fallback: bool = False              # a window was decoded again at a higher temperature
     stt_hotword: bool = False               # the transcript contains a configured hotword
     # STT engine with timestamps (else None): (start_s, end_s, text) segments in
@@ -159,12 +163,14 @@ class VoicePipeline:
             segments=r.segments, speech_start_s=r.speech_start_s, speech_end_s=r.speech_end_s,
             temperature=max(r.temperatures) if r.temperatures else None,
             compression_ratio=max(r.compression_ratios) if r.compression_ratios else None,
-            words=r.words, hotwords=r.hotwords)
+            words=r.words, hotwords=r.hotwords, vad_spans=r.vad_spans,
+            vad_speech_s=r.vad_speech_s, vad_silent=r.vad_silent)
         j.stt_fallback = r.fallback_attempts > 0
         j.stt_hotword = bool(r.hotwords)
         j.segments, j.open_segments = r.segments, r.open_segments
         j.words = r.words
-        j.no_speech = r.gated_windows > 0 and r.gated_windows == r.windows
+        j.no_speech = r.vad_silent or (r.gated_windows > 0 and r.gated_windows == r.windows)
+        j.vad_silent = r.vad_silent
 
     def build_request(self, j: PipelineJob) -> GenRequest | None:
         if j.stt_failed:

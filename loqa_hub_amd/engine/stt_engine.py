@@ -11,6 +11,7 @@ of the same length; only the fed-back token is the reference one.
 """
 from __future__ import annotations
 
+import collections
 import logging
 import os
 import queue
@@ -197,6 +198,20 @@ class STTRequest:
     # occurrence
     hotwords: list | None = None
     hypothesis_traces: list = field(default_factory=list)
+    # where each window starts in the utterance, seconds: 30 w for the fixed
+    # 30 s windows, the plan's ``a * 0.02`` with VAD (set by ``upload``)
+    win_starts: list = field(default_factory=list)
+    # STTEngine(vad=VadConfig(...)), free decoding (None / False with the
+    # feature off and for teacher-forced requests): the detector's speech spans
+    # as (start_s, end_s) in utterance time, clamped to the duration; the speech
+    # they hold in seconds; ``vad_silent``: no span at all - the utterance took
+    # no encoder row and no decoder step, its text is empty and ``windows`` is 0
+    vad_spans: list | None = None
+    vad_speech_s: float | None = None
+    vad_silent: bool = False
+    # engine-owned: the window plan, (a, b) in 20 ms frames per window (None:
+    # fixed 30 s windows)
+    win_frames: list | None = None
 
 
 class STTEngine:
@@ -221,8 +236,23 @@ class STTEngine:
                  timestamps: bool = False, max_initial_timestamp: float = 1.0,
                  temperatures=(0.0,), compression_ratio_threshold: float = 2.4,
                  word_timestamps: bool = False, alignment_heads=None, beam_size: int = 1,
-                 hotwords=None, hotword_boost: float = 2.0):
+                 hotwords=None, hotword_boost: float = 2.0, vad=None):
         self.cfg = cfg
+        # voice activity detection (engine/stt_vad.py): ``upload`` runs ops.vad
+        # over the PCM of the freely decoded utterances once it is on the device,
+        # reads the speech spans back and builds the encoder rows from a window
+        # plan that starts and ends at speech and cuts at pauses; an utterance
+        # without speech takes no encoder row. None: off - no field, no buffer,
+        # no launch and no host read beyond the plain engine's.
+        from .stt_vad import VadConfig
+        if vad is not None and not isinstance(vad, VadConfig):
+            raise ValueError(f"STT vad: a VadConfig or None, not {type(vad).__name__}")
+        self.vad = vad
+        self.vad_params = vad.params if vad is not None else None
+        self._vad_host = None           # pinned read-back buffer, grown on demand
+        # cross-attention slots a VAD plan did not need, handed back by the
+        # encoder thread and reclaimed by the scheduler
+        self._spare_slots: collections.deque = collections.deque()
         # hotword biasing (engine/hotwords.py): every decoder step ends, before
         # the sampler, with ops.hotword_step, which advances the sequence's node
         # of the phrase automaton by the token it sampled last (``hw_state`` and
@@ -394,6 +424,9 @@ class STTEngine:
             self.stats.update(fallback_windows=0, fallback_attempts=0)
         if self.beam_size > 1:
             self.stats.update(beam_windows=0, beam_kv_copies=0)
+        if self.vad is not None:
+            self.stats.update(vad_utterances=0, vad_silent_utterances=0, vad_plan_fallbacks=0,
+                              vad_windows_saved=0)
         self.hw_table = self.hw_auto = None
         self._live_reqs = None
         if self.hotwords_on:
@@ -541,7 +574,17 @@ class STTEngine:
         any request of the batch is not 16 kHz the launch is
         ``ops.pcm16_resample_padded`` (one for the whole batch, 16 kHz requests
         pass through), otherwise ``ops.pcm16_to_f32_padded`` as ever. Windows,
-        ``n_samples`` and the dropped-sample count are in 16 kHz samples."""
+        ``n_samples`` and the dropped-sample count are in 16 kHz samples.
+
+        An engine with ``vad``: the freely decoded requests of the batch go
+        through ``ops.vad`` once the PCM is on the device, their spans are read
+        back once and their rows follow the window plan (``_vad_plan``): window
+        ``(a, b)`` is the 16 kHz samples [320 a, min(320 b, n)) of the
+        utterance, a silent utterance has no row. Such a batch is converted by
+        ``ops.pcm16_resample_padded`` whatever its rates; a batch without a VAD
+        request launches what the plain engine launches. The returned sums of
+        squares (and ``STTRequest.sumsq`` / ``rms`` made of them) are those of
+        the rows actually written: with VAD, of the planned windows only."""
         lens = []
         for r in reqs:
             n = self._n_out(r)          # everything below counts 16 kHz samples
@@ -554,6 +597,8 @@ class STTEngine:
                           self.max_windows, (n - w * N_SAMPLES) / 16000)
             lens.append(min(n, w * N_SAMPLES))
             r.windows = w
+            r.win_starts = [30.0 * i for i in range(w)]
+            r.win_frames, r.vad_spans, r.vad_speech_s, r.vad_silent = None, None, None, False
         for r, n in zip(reqs, lens):
             r.n_samples = n
         rates = [r.sample_rate or 16000 for r in reqs]
@@ -597,6 +642,14 @@ class STTEngine:
                 if r.staged is not None:
                     r.staged.release()
                     r.staged = None
+        if self.vad is not None and self._vad_plan(reqs, pcm, offs, lens, out_lens, rates):
+            # rows from the window plans (teacher-forced requests: fixed windows)
+            rows = []
+            for r, o, n_src, n, sr in zip(reqs, offs[:-1], lens, out_lens, rates):
+                wins = r.win_frames if r.win_frames is not None else \
+                    [(w * 1500, (w + 1) * 1500) for w in range(r.windows)]
+                rows += [(int(o), n_src, a * 320, min(b * 320, n) - a * 320, sr) for a, b in wins]
+            return ops.pcm16_resample_padded(pcm, rows, N_SAMPLES)
         if resampled:
             # one launch for the whole batch: a row is a 30 s window of its
             # utterance's 16 kHz signal (16 kHz utterances pass through)
@@ -624,6 +677,61 @@ class STTEngine:
         """Source samples the first ``n_out`` 16 kHz outputs read."""
         _, L, M, T = ops.ref.resample_filter(rate, 16000)
         return 0 if n_out <= 0 else (n_out - 1) * M // L + (T - 1) // 2 + 1
+
+    def _vad_plan(self, reqs: list[STTRequest], pcm: torch.Tensor, offs, lens, out_lens,
+                  rates) -> bool:
+        """``ops.vad`` over the freely decoded requests of an uploaded batch
+        (request i is ``pcm[offs[i] : offs[i] + lens[i]]`` at ``rates[i]``, and
+        ``out_lens[i]`` 16 kHz samples), one read-back of the spans through
+        pinned memory, and each request's window plan: ``win_frames``,
+        ``windows`` (0: silent), ``win_starts`` and the ``vad_*`` results.
+        ``r.windows`` comes in as the slots admission reserved for it. False: the
+        batch has no such request and nothing was launched."""
+        from .stt_vad import FRAME_HZ, clip_spans, plan_windows_counted, spans_seconds
+        idx = [i for i, r in enumerate(reqs)
+               if r.transcript is None and r.transcript_windows is None]
+        if not idx:
+            return False
+        descs, f0 = [], 0
+        for i in idx:
+            descs.append((int(offs[i]), int(lens[i]), int(rates[i]), f0))
+            f0 += ops.ref.vad_frames(lens[i], rates[i])
+        U = len(idx)
+        cap = max(ops.ref.vad_frames(d[1], d[2]) for d in descs) // 2 + 1
+        # spans, n_spans and speech_frames in one buffer: one copy reads them all
+        n_sp = U * cap * 2
+        buf = torch.empty(n_sp + 2 * U, dtype=torch.int32, device=pcm.device)
+        E = torch.zeros(max(f0, 1), dtype=torch.int32, device=pcm.device)
+        ops.vad(pcm, descs, self.vad_params,
+                out=(E, buf[:n_sp].view(U, cap, 2), buf[n_sp:n_sp + U], buf[n_sp + U:]))
+        if self.is_gpu:
+            if self._vad_host is None or self._vad_host.numel() < buf.numel():
+                self._vad_host = torch.empty(max(4096, 2 * buf.numel()),
+                                             dtype=torch.int32).pin_memory()
+            host = self._vad_host[: buf.numel()]
+            host.copy_(buf, non_blocking=True)
+            torch.cuda.current_stream(self.device).synchronize()
+            h = host.numpy()
+        else:
+            h = buf.numpy()
+        spans = h[:n_sp].reshape(U, cap, 2)
+        n_spans, speech = h[n_sp:n_sp + U], h[n_sp + U:]
+        for u, i in enumerate(idx):
+            r, n = reqs[i], out_lens[i]
+            dur = n / 16000.0
+            sp = clip_spans(spans[u, : int(n_spans[u])].tolist(), -(-n // 320))
+            reserved = r.windows
+            plan, fell_back = plan_windows_counted(sp, reserved)
+            self.stats["vad_utterances"] += 1
+            self.stats["vad_plan_fallbacks"] += fell_back
+            self.stats["vad_windows_saved"] += reserved - len(plan)
+            r.win_frames = plan
+            r.windows = len(plan)
+            r.win_starts = [a / FRAME_HZ for a, _ in plan]
+            r.vad_spans = spans_seconds(sp, dur)
+            r.vad_speech_s = min(int(speech[u]) / FRAME_HZ, dur)
+            r.vad_silent = not plan
+        return True
 
     @staticmethod
     def _host_samples(r: STTRequest) -> np.ndarray:
@@ -1071,9 +1179,13 @@ class STTEngine:
         with tr.span("h2d", dev, batch=len(reqs)):
             audio, sumsq = self.upload(reqs, device_pcm)
         t0 = time.perf_counter()
+        # a VAD plan may need fewer rows than the slots reserved for the batch
+        # (none at all when every utterance is silent: no encoder pass)
+        slots, spare = list(slots[: audio.shape[0]]), list(slots[audio.shape[0]:])
         with tr.span("encode", dev, batch=len(reqs)):
-            enc = self.encode(audio)
-            self.cross_kv(enc, slots)
+            if slots:
+                enc = self.encode(audio)
+                self.cross_kv(enc, slots)
         ss = sumsq.cpu().numpy()
         if self.is_gpu:
             torch.cuda.current_stream(self.device).synchronize()
@@ -1088,8 +1200,16 @@ class STTEngine:
             r.sumsq = float(ss[i:i + w].sum())
             r.rms = float(np.sqrt(r.sumsq / n))
             r.slots = list(slots[i:i + w])
-            r.slot = r.slots[0]
+            r.slot = r.slots[0] if w else -1
             i += w
+        self._spare_slots.extend(spare)
+
+    def _reclaim_spare(self) -> None:
+        """Slots a VAD plan left unused go back to the scheduler's free list."""
+        if self._spare_slots:
+            while self._spare_slots:
+                self._free_slots.append(self._spare_slots.popleft())
+            self._free_slots.sort()
 
     def _start_decode(self, reqs: list[STTRequest]) -> None:
         """Decoder sequences for encoded requests (scheduler thread)."""
@@ -1115,6 +1235,13 @@ class STTEngine:
             if self.timestamps:
                 r.segments, r.open_segments = [], []
             r.hotwords = [] if self.hotwords_on else None
+            if r.vad_silent:
+                # no span: no encoder row, no decoder sequence - done here
+                r.text, r.tokens, r.logprobs = "", [], []
+                r.t_done = time.perf_counter()
+                self.stats["vad_silent_utterances"] += 1
+                self.stats["utterances"] += 1
+                continue
             if self._live_reqs is not None:
                 self._live_reqs.add(r)
             if not r.slots:
@@ -1300,7 +1427,8 @@ class STTEngine:
             r.win_texts.append("")
         elif segs is not None:
             out = utterance_segments(segs, r.win, r.n_samples / 16000.0,
-                                     lambda t: self.tok.decode(t, skip_from=self.ts_begin))
+                                     lambda t: self.tok.decode(t, skip_from=self.ts_begin),
+                                     *self._win_span(r))
             if self.align is not None:
                 # per text token the index of its segment in ``r.segments``
                 # (None: a segment dropped for its empty text)
@@ -1402,8 +1530,21 @@ class STTEngine:
 
     def window_frames(self, r: STTRequest) -> int:
         """20 ms frames of the audio in ``r``'s current window."""
+        if r.win_frames is not None:
+            a, b = r.win_frames[r.win]
+            return ops.ref.align_frames(min(b * 320, r.n_samples) - a * 320, self.cfg.n_audio_ctx)
         return ops.ref.align_frames(min(N_SAMPLES, r.n_samples - r.win * N_SAMPLES),
                                     self.cfg.n_audio_ctx)
+
+    @staticmethod
+    def _win_span(r: STTRequest) -> tuple:
+        """(start, end) of ``r``'s current window in utterance seconds, as
+        ``utterance_segments`` / ``utterance_words`` take them: ``win_starts``
+        and, for a planned window, its end (None: the utterance's duration
+        bounds it, as for the fixed 30 s windows)."""
+        off = r.win_starts[r.win] if r.win < len(r.win_starts) else None
+        end = r.win_frames[r.win][1] / 50 if r.win_frames is not None else None
+        return off, end
 
     def _align_window(self, r: STTRequest, seg_of: list | None) -> None:
         """Word timestamps of ``r``'s kept window: three launches on this
@@ -1426,7 +1567,7 @@ class STTEngine:
         words = window_words(self.tok.decode, [r.tokens[k] for k in idx], frames[: len(idx)],
                              frames[len(idx)] if eot_k is not None else F, lps,
                              r.language or self.language, seg_of)
-        r.words += utterance_words(words, r.win, r.n_samples / 16000.0)
+        r.words += utterance_words(words, r.win, r.n_samples / 16000.0, *self._win_span(r))
         r.word_segments += [w.segment for w in words]
         self.stats["aligned_windows"] += 1
         self.stats["aligned_words"] += len(words)
@@ -1439,8 +1580,9 @@ class STTEngine:
         rows = self.rows_needed(reqs)
         assert rows <= self.max_slots, "batch (30 s windows) exceeds max_batch"
         self._admit(reqs, list(range(rows)), device_pcm)
+        self._spare_slots.clear()       # no scheduler: the slots were this call's own
         t_dec = time.monotonic()
-        live, steps = list(reqs), 0
+        live, steps = [r for r in reqs if r.t_done == 0.0], 0
         while live:
             self._decode_once(live)
             steps += 1
@@ -1541,7 +1683,9 @@ class STTEngine:
                     waiting.append(it)
             try:
                 new: list[STTRequest] = []
+                quiet: list[STTRequest] = []      # VAD-silent: finished at admission
                 n_rows = 0
+                self._reclaim_spare()
                 # FIFO, except that items which fit may pass a head that does
                 # not (a long-form utterance waiting for many free slots), at
                 # most HOL_BYPASS times per head so it is never starved
@@ -1579,6 +1723,9 @@ class STTEngine:
                         encoding.append((new, enc_pool.submit(self._encode, new, slots)))
                     else:
                         self._admit(new, slots)
+                        self._reclaim_spare()
+                        quiet += [r for r in new if r.t_done != 0.0]
+                        new = [r for r in new if r.t_done == 0.0]
                         if pl is not None:
                             for r in new:
                                 pl.admit(r)
@@ -1591,6 +1738,9 @@ class STTEngine:
                         if f.done():
                             f.result()
                             self._start_decode(reqs)
+                            self._reclaim_spare()
+                            quiet += [r for r in reqs if r.t_done != 0.0]
+                            reqs = [r for r in reqs if r.t_done == 0.0]
                             if pl is not None:
                                 for r in reqs:
                                     pl.admit(r)
@@ -1598,10 +1748,13 @@ class STTEngine:
                         else:
                             still.append((reqs, f))
                     encoding = still
-                if live:
-                    finished = pl.pump(live) if pl is not None else self._decode_once(live)
+                if live or quiet:
+                    finished = quiet
+                    if live:
+                        finished = quiet + (pl.pump(live) if pl is not None
+                                            else self._decode_once(live))
                     for r in finished:
-                        self._free_slots += r.slots or [r.slot]
+                        self._free_slots += [] if r.vad_silent else r.slots or [r.slot]
                         self._free_slots.sort()
                         cell = r.on_done
                         if cell[3] is not None:
@@ -1630,6 +1783,7 @@ class STTEngine:
                 live, waiting, cells, encoding = [], [], {}, []
                 if self._live_reqs is not None:
                     self._live_reqs.clear()
+                self._spare_slots.clear()
                 self._free_slots = list(range(self.max_slots))
 
     def _encoder_executor(self) -> ThreadPoolExecutor:

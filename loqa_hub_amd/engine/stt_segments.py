@@ -57,13 +57,18 @@ def text_tokens(tokens, ts_begin: int, eot: int | None = None) -> list[int]:
     return [int(t) for t in tokens if int(t) < ts_begin and (eot is None or int(t) != eot)]
 
 
-def utterance_segments(segs: list[Segment], window: int, duration_s: float, decode
+def utterance_segments(segs: list[Segment], window: int, duration_s: float, decode,
+                       offset_s: float | None = None, end_s: float | None = None
                        ) -> list[tuple[float, float, str]]:
     """``(start_s, end_s, text)`` in utterance time for window ``window``'s
     segments: offset by 30 s per window, clamped to the utterance's duration;
-    segments whose text is empty are dropped."""
+    segments whose text is empty are dropped. ``offset_s`` / ``end_s``: where
+    the window starts and ends in the utterance when it is not a fixed 30 s one
+    (``STTRequest.win_starts``, a VAD window plan); times are clamped to its end."""
     out = []
-    off = window * WINDOW_S
+    off = window * WINDOW_S if offset_s is None else offset_s
+    if end_s is not None:
+        duration_s = min(duration_s, end_s)
     for s in segs:
         text = decode(s.tokens).strip()
         if not text:

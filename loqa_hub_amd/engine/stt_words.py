@@ -166,10 +166,15 @@ def window_words(decode, tokens, frames, end_frame: int, logprobs=None,
     return merge_punctuations(out)
 
 
-def utterance_words(words: list, window: int, duration_s: float) -> list:
+def utterance_words(words: list, window: int, duration_s: float,
+                    offset_s: float | None = None, end_s: float | None = None) -> list:
     """``(start_s, end_s, word, probability)`` in utterance time: + 30 s per
-    window, clamped to the utterance's duration."""
-    off = window * WINDOW_S
+    window, clamped to the utterance's duration. ``offset_s`` / ``end_s``: the
+    window's own start and end in the utterance (``STTRequest.win_starts``, a
+    VAD window plan) instead of 30 s per window; times are clamped to its end."""
+    off = window * WINDOW_S if offset_s is None else offset_s
+    if end_s is not None:
+        duration_s = min(duration_s, end_s)
     out = []
     for w in words:
         a = min(off + w.start_s, duration_s)

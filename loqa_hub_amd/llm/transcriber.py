@@ -53,6 +53,12 @@ class TranscriptionResult:
     # HUB_STT_HOTWORDS (gpu backend; else None): the configured phrases that the
     # decoder's text contains, in order of first occurrence
     hotwords: list | None = None
+    # HUB_STT_VAD=on (gpu backend; else None): the detector's speech spans as
+    # (start_s, end_s) in utterance time, the speech they hold in seconds, and
+    # whether the utterance had none at all (it was not transcribed)
+    vad_spans: list | None = None
+    vad_speech_s: float | None = None
+    vad_silent: bool = False
 
 
 @dataclass
@@ -135,7 +141,9 @@ def to_transcription_result(raw: str, avg_logprob: float | None = None,
                             temperature: float | None = None,
                             compression_ratio: float | None = None,
                             words: list | None = None,
-                            hotwords: list | None = None) -> TranscriptionResult:
+                            hotwords: list | None = None, vad_spans: list | None = None,
+                            vad_speech_s: float | None = None,
+                            vad_silent: bool = False) -> TranscriptionResult:
     """``avg_logprob`` (the on-device Whisper decode's mean token
     log-probability): the confidence is the geometric-mean token probability
     ``min(1, exp(avg_logprob))`` instead of the text heuristic, and a
@@ -148,12 +156,14 @@ def to_transcription_result(raw: str, avg_logprob: float | None = None,
     ``temperature`` / ``compression_ratio`` of a decode with temperature fallback,
     and ``words`` of a decode with word timestamps, from which ``command_start_s``
     (the wake-word cut in seconds) is read, and ``hotwords`` of a decode with
-    hotword biasing."""
+    hotword biasing, and ``vad_spans`` / ``vad_speech_s`` / ``vad_silent`` of an
+    engine with voice activity detection."""
     p = post_process_transcription(raw)
     probe = dict(language=language, language_prob=language_prob, no_speech_prob=no_speech_prob,
                  segments=segments, speech_start_s=speech_start_s, speech_end_s=speech_end_s,
                  temperature=temperature, compression_ratio=compression_ratio, words=words,
-                 hotwords=hotwords,
+                 hotwords=hotwords, vad_spans=vad_spans, vad_speech_s=vad_speech_s,
+                 vad_silent=vad_silent,
                  command_start_s=command_start(words, p.wake_word_variant)
                  if p.wake_word_detected else None)
     if avg_logprob is None:

@@ -1024,6 +1024,81 @@ def pcm16_resample(pcm: torch.Tensor, lens: torch.Tensor, rate_in: int, rate_out
     return out, n_out
 
 
+# voice activity detection (csrc/kernels/vad.hip)
+VadParams = ref.VadParams
+vad_params = ref.vad_params
+
+
+def vad_tile() -> int:
+    """Frames per tile of the spans kernel (its workgroup walks longer
+    utterances tile by tile)."""
+    return int(kernels().loqa_vad_tile())
+
+
+def vad(pcm: torch.Tensor, descs, params: "ref.VadParams", out=None
+        ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Voice activity of the utterances in ``pcm`` (int16 [N], concatenated).
+    ``descs``: one host tuple (src_first, src_len, rate, frame_first) per
+    utterance - pcm[src_first : src_first + src_len] at ``rate`` (one of
+    RESAMPLE_RATES), its 20 ms frames at ``frame_first`` of the frame array.
+    ``params``: ``vad_params(...)``. Returns (E int32 [frames]: the frames'
+    mean squares, at most 2^30; spans int32 [U, cap, 2]: the speech runs as
+    [start, end) frames, cap = F_max // 2 + 1; n_spans int32 [U];
+    speech_frames int32 [U]) - the values of ``ref.vad``, bit for bit. Rows of
+    ``spans`` beyond ``n_spans`` are not written (-1 on the CPU).
+
+    On the GPU: two launches on the current stream, no host synchronisation;
+    the results stay on the device. ``out`` = (E, spans, n_spans,
+    speech_frames) to write into. A wrong dtype, a non-contiguous tensor, a
+    descriptor outside ``pcm`` or the frame array, an unsupported rate or a
+    parameter out of range: ValueError before anything is launched."""
+    import numpy as np
+    if not isinstance(pcm, torch.Tensor) or pcm.dtype != torch.int16 or pcm.dim() != 1 or \
+            not pcm.is_contiguous():
+        raise ValueError("vad: pcm must be a contiguous 1-D int16 tensor")
+    if not isinstance(params, ref.VadParams):
+        raise ValueError("vad: params must be VadParams (ops.vad_params)")
+    ref.check_vad_params(params)
+    if out is not None:
+        if len(out) != 4 or any(not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or
+                                not t.is_contiguous() or t.device != pcm.device for t in out):
+            raise ValueError("vad: out must be four contiguous int32 tensors on pcm's device")
+    descs = ref.vad_check_descs(descs, pcm.numel(), None if out is None else out[0].numel())
+    U = len(descs)
+    Fs = [ref.vad_frames(n, r) for _, n, r, _ in descs]
+    F_max = max(Fs + [0])
+    cap = F_max // 2 + 1
+    if out is not None:
+        sp, ns, sf = out[1], out[2], out[3]
+        if sp.dim() != 3 or sp.shape[0] < U or sp.shape[1] < cap or sp.shape[2] != 2 or \
+                ns.numel() < U or sf.numel() < U:
+            raise ValueError(f"vad: out holds fewer than {U} utterances of {cap} spans")
+    if not _gpu(pcm):
+        return ref.vad(pcm, descs, params, out)
+    dev = pcm.device
+    if out is None:
+        total = max([d[3] + F for d, F in zip(descs, Fs)] + [0])
+        out = (torch.zeros(max(total, 1), dtype=torch.int32, device=dev)[:total],
+               torch.empty(max(U, 1), cap, 2, dtype=torch.int32, device=dev)[:U],
+               torch.empty(max(U, 1), dtype=torch.int32, device=dev)[:U],
+               torch.empty(max(U, 1), dtype=torch.int32, device=dev)[:U])
+    if U == 0:
+        return out
+    E, spans, n_spans, speech = out
+    desc = np.asarray(descs, np.int64).reshape(U, 4)
+    d_dev = torch.from_numpy(desc).pin_memory().to(dev, non_blocking=True)
+    prm = np.asarray(params.ints(), np.int32)
+    ws_words = ref.VAD_WS_WORDS * U * max(F_max, 1)
+    ws = torch.empty(ws_words, dtype=torch.int32, device=dev)
+    k, st = kernels(), stream_ptr(pcm)
+    check(k.loqa_vad_energy(ptr(pcm), pcm.numel(), ptr(d_dev), desc.ctypes.data, U, ptr(E),
+                            E.numel(), st), "vad_energy")
+    check(k.loqa_vad_spans(ptr(d_dev), desc.ctypes.data, U, ptr(E), E.numel(), prm.ctypes.data,
+                           ptr(ws), ws_words, ptr(spans), spans.shape[1], ptr(n_spans),
+                           ptr(speech), st), "vad_spans")
+    return out
+
+
 FLAC_BLOCKS = ref.FLAC_BLOCKS
 
 

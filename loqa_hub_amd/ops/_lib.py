@@ -213,6 +213,13 @@ _KERNEL_SIGS = {
                           c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                           c_void_p],
     "loqa_hotword_wg": [],
+    # (pcm, pcm_len, descs, descs_host, U, E, E_cap, stream)
+    "loqa_vad_energy": [c_void_p, c_ll, c_void_p, c_void_p, c_int, c_void_p, c_ll, c_void_p],
+    # (descs, descs_host, U, E, E_cap, params_host, ws, ws_words, spans, cap, n_spans,
+    #  speech_frames, stream)
+    "loqa_vad_spans": [c_void_p, c_void_p, c_int, c_void_p, c_ll, c_void_p, c_void_p, c_ll,
+                       c_void_p, c_int, c_void_p, c_void_p, c_void_p],
+    "loqa_vad_tile": [],
 }
 
 # (argtypes, restype) of the custom all-reduce entry points (in the kernels library)

@@ -1856,3 +1856,199 @@ def hotword_step(logits, V: int, hw_ctl, row_slot, hw_state, last_tok, auto) -> 
             idx = torch.tensor(cols, dtype=torch.long)
             x = logits[b, idx]
             logits[b, idx] = torch.where(torch.isnan(x), x, (x.float() + boost).to(logits.dtype))
+
+
+# ------------------------------------------------- voice activity detection
+# The model of csrc/kernels/vad.hip, which must give these values exactly:
+# everything is integer arithmetic (docs/ARCHITECTURE.md "Voice activity
+# detection" states the rules).
+VAD_FRAME_HZ = 50                # 20 ms frames: one encoder position each
+VAD_WS_WORDS = 6                 # kernel workspace, int32 words per frame
+VAD_MAX_FLOOR_FRAMES = 3000      # W: 60 s a side
+VAD_MAX_RUN_FRAMES = 500         # min_speech, min_silence, pad: 10 s
+
+
+@dataclass(frozen=True)
+class VadParams:
+    """The detector's integer parameters, as the kernel gets them."""
+    level_min: int       # E below it is never speech: round(2^30 10^(dBFS / 10))
+    floor_max: int       # cap on the noise floor, the same scale
+    ratio_q: int         # speech needs E * 256 > floor * ratio_q: round(256 10^(dB / 10))
+    W: int               # noise-floor window, frames a side
+    min_speech: int      # shortest speech run kept, frames
+    min_silence: int     # gaps shorter than this are filled, frames
+    pad: int             # padding around speech, frames
+
+    def ints(self) -> tuple:
+        return (self.level_min, self.floor_max, self.ratio_q, self.W, self.min_speech,
+                self.min_silence, self.pad)
+
+
+def check_vad_params(p: VadParams) -> VadParams:
+    """Range check of the integer parameters (ValueError), as the launcher's."""
+    lim = (("level_min", 0, 1 << 30), ("floor_max", 0, 1 << 30), ("ratio_q", 256, 2560000),
+           ("W", 0, VAD_MAX_FLOOR_FRAMES), ("min_speech", 1, VAD_MAX_RUN_FRAMES),
+           ("min_silence", 0, VAD_MAX_RUN_FRAMES), ("pad", 0, VAD_MAX_RUN_FRAMES))
+    for name, lo, hi in lim:
+        v = getattr(p, name)
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+            raise ValueError(f"VAD parameter {name} = {v!r} is outside {lo}..{hi}")
+    return p
+
+
+def _vad_frames_of_ms(name: str, ms, lo: int) -> int:
+    if isinstance(ms, bool) or not isinstance(ms, (int, float)) or ms != int(ms) or int(ms) % 20:
+        raise ValueError(f"VAD {name} = {ms!r} ms must be a multiple of 20")
+    n = int(ms) // 20
+    if not lo <= n <= VAD_MAX_RUN_FRAMES:
+        raise ValueError(f"VAD {name} = {ms} ms is outside {20 * lo}..{20 * VAD_MAX_RUN_FRAMES}")
+    return n
+
+
+def vad_params(threshold_db: float = 9.0, min_level_dbfs: float = -55.0,
+               floor_max_dbfs: float = -30.0, floor_s: float = 3.0, min_speech_ms: int = 100,
+               min_silence_ms: int = 500, pad_ms: int = 200) -> VadParams:
+    """dB, seconds and milliseconds -> ``VadParams``. threshold_db in [0, 40]
+    (above the noise floor); the two levels in [-100, 0] dBFS, where 0 dBFS is a
+    mean square of 2^30; floor_s in [0, 60]; the millisecond values multiples of
+    20, min_speech_ms at least 20, each at most 10 s. ValueError otherwise."""
+    def num(name, v, lo, hi):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or \
+                not lo <= v <= hi:
+            raise ValueError(f"VAD {name} = {v!r} is outside [{lo}, {hi}]")
+        return float(v)
+    thr = num("threshold_db", threshold_db, 0.0, 40.0)
+    lvl = num("min_level_dbfs", min_level_dbfs, -100.0, 0.0)
+    cap = num("floor_max_dbfs", floor_max_dbfs, -100.0, 0.0)
+    fs = num("floor_s", floor_s, 0.0, VAD_MAX_FLOOR_FRAMES / VAD_FRAME_HZ)
+    return check_vad_params(VadParams(
+        level_min=int(round((1 << 30) * 10.0 ** (lvl / 10.0))),
+        floor_max=int(round((1 << 30) * 10.0 ** (cap / 10.0))),
+        ratio_q=int(round(256 * 10.0 ** (thr / 10.0))),
+        W=int(round(fs * VAD_FRAME_HZ)),
+        min_speech=_vad_frames_of_ms("min_speech_ms", min_speech_ms, 1),
+        min_silence=_vad_frames_of_ms("min_silence_ms", min_silence_ms, 0),
+        pad=_vad_frames_of_ms("pad_ms", pad_ms, 0)))
+
+
+def vad_frames(n: int, rate: int) -> int:
+    """20 ms frames of ``n`` samples at ``rate``: ceil(n * 50 / rate)."""
+    return -(-int(n) * VAD_FRAME_HZ // int(rate))
+
+
+def vad_check_descs(descs, pcm_len: int, frames_cap: int | None = None) -> list:
+    """``descs`` as tuples of ints (src_first, src_len, rate, frame_first),
+    checked: a supported rate, the utterance inside the ``pcm_len`` samples,
+    its frames inside ``frames_cap`` (when given) and apart from every other
+    utterance's. ValueError otherwise."""
+    out = [tuple(int(v) for v in d) for d in descs]
+    spans = []
+    for d in out:
+        if len(d) != 4:
+            raise ValueError(f"VAD descriptor {d}: (src_first, src_len, rate, frame_first)")
+        s0, n, rate, f0 = d
+        check_rate(rate)
+        if s0 < 0 or n < 0 or f0 < 0 or s0 + n > pcm_len:
+            raise ValueError(f"VAD descriptor {d} is outside the PCM ({pcm_len} samples)")
+        F = vad_frames(n, rate)
+        if frames_cap is not None and f0 + F > frames_cap:
+            raise ValueError(f"VAD descriptor {d}: frames [{f0}, {f0 + F}) exceed the frame "
+                             f"array ({frames_cap})")
+        if F:
+            spans.append((f0, f0 + F))
+    spans.sort()
+    for (_, e0), (s1, _) in zip(spans, spans[1:]):
+        if s1 < e0:
+            raise ValueError("VAD descriptors: the utterances' frame ranges overlap")
+    return out
+
+
+def vad_energy(pcm, descs, out=None) -> np.ndarray:
+    """Frame energies, uint32: E[frame_first + f] = floor(sum x^2 / count) over
+    the source samples [f * rate // 50, min(n, (f + 1) * rate // 50)) of each
+    utterance, f < ceil(n * 50 / rate). ``out``: the frame array to write into
+    (only the utterances' frames change); default: zeros up to the last frame."""
+    x = pcm.numpy() if isinstance(pcm, torch.Tensor) else np.asarray(pcm)
+    descs = vad_check_descs(descs, x.shape[0], None if out is None else out.shape[0])
+    if out is None:
+        out = np.zeros(max([f0 + vad_frames(n, r) for _, n, r, f0 in descs] + [0]), np.uint32)
+    for s0, n, rate, f0 in descs:
+        F = vad_frames(n, rate)
+        if F == 0:
+            continue
+        edges = np.minimum(np.arange(F + 1, dtype=np.int64) * rate // VAD_FRAME_HZ, n)
+        sq = x[s0:s0 + n].astype(np.int64) ** 2
+        csum = np.zeros(n + 1, np.int64)
+        np.cumsum(sq, out=csum[1:])              # < 2^30 * 2^33: exact in int64
+        out[f0:f0 + F] = ((csum[edges[1:]] - csum[edges[:-1]]) // np.diff(edges)).astype(np.uint32)
+    return out
+
+
+def _runs(s: np.ndarray) -> list:
+    """Maximal runs of True in the bool vector ``s`` as [start, end) pairs."""
+    d = np.diff(np.concatenate(([0], s.astype(np.int8), [0])))
+    return list(zip(np.flatnonzero(d == 1).tolist(), np.flatnonzero(d == -1).tolist()))
+
+
+def vad_raw(E, p: VadParams) -> np.ndarray:
+    """The raw per-frame decision of one utterance's energies (bool [F]):
+    N[f] = min(floor_max, min E[g] for |g - f| <= W inside the utterance),
+    raw[f] = E[f] >= level_min and E[f] * 256 > N[f] * ratio_q."""
+    E = np.asarray(E, np.uint32).astype(np.uint64)
+    F = E.shape[0]
+    N = np.empty(F, np.uint64)
+    for f in range(F):
+        N[f] = E[max(0, f - p.W):f + p.W + 1].min()
+    N = np.minimum(N, np.uint64(p.floor_max))
+    return (E >= np.uint64(p.level_min)) & (E * np.uint64(256) > N * np.uint64(p.ratio_q))
+
+
+def vad_smooth(raw, p: VadParams) -> np.ndarray:
+    """Close, open, pad - each on the result of the one before (bool [F])."""
+    s = np.array(raw, bool)
+    F = s.shape[0]
+    for a, b in _runs(~s):                       # close: inner gaps shorter than min_silence
+        if a > 0 and b < F and b - a < p.min_silence:
+            s[a:b] = True
+    for a, b in _runs(s):                        # open: speech runs shorter than min_speech
+        if b - a < p.min_speech:
+            s[a:b] = False
+    out = s.copy()
+    for a, b in _runs(s):                        # pad, clipped to the utterance
+        out[max(0, a - p.pad):min(F, b + p.pad)] = True
+    return out
+
+
+def vad_spans(E, F: int, p: VadParams) -> tuple[np.ndarray, int]:
+    """(int32 [n, 2] spans as [start, end) frames, ascending; speech frames) of
+    one utterance: ``E[:F]`` are its frame energies."""
+    check_vad_params(p)
+    s = vad_smooth(vad_raw(np.asarray(E)[:F], p), p)
+    return np.asarray(_runs(s), np.int32).reshape(-1, 2), int(s.sum())
+
+
+def vad(pcm, descs, p: VadParams, out=None):
+    """Energies and spans of every utterance (the CPU path of ``ops.vad``):
+    (E uint32 [frames] as int32 bits, spans int32 [U, cap, 2], n_spans int32
+    [U], speech_frames int32 [U]) as tensors, cap = F_max // 2 + 1. Entries of
+    ``spans`` beyond ``n_spans`` are -1, or stay as they are in ``out`` = (E,
+    spans, n_spans, speech_frames), which is then written in place."""
+    check_vad_params(p)
+    x = pcm.numpy() if isinstance(pcm, torch.Tensor) else np.asarray(pcm)
+    descs = vad_check_descs(descs, x.shape[0], None if out is None else out[0].numel())
+    Fs = [vad_frames(n, r) for _, n, r, _ in descs]
+    U, cap = len(descs), max(Fs + [0]) // 2 + 1
+    if out is None:
+        total = max([d[3] + F for d, F in zip(descs, Fs)] + [0])
+        out = (torch.zeros(total, dtype=torch.int32),
+               torch.full((U, cap, 2), -1, dtype=torch.int32),
+               torch.zeros(U, dtype=torch.int32), torch.zeros(U, dtype=torch.int32))
+    E_t, spans_t, n_t, sf_t = out
+    E = E_t.numpy().view(np.uint32)
+    vad_energy(x, descs, E)
+    for u, (d, F) in enumerate(zip(descs, Fs)):
+        sp, n_speech = vad_spans(E[d[3]:d[3] + F], F, p)
+        spans_t[u, :len(sp)] = torch.from_numpy(sp)
+        n_t[u] = len(sp)
+        sf_t[u] = n_speech
+    return E_t, spans_t, n_t, sf_t

@@ -143,7 +143,7 @@ def build_gpu_processor(cfg: Config, nats, device: str = "cuda:0", tts=None, *, 
                     word_timestamps=g.stt_word_timestamps == "on",
                     alignment_heads=g.stt_alignment_heads or None, beam_size=g.stt_beam_size,
                     hotwords=resolve_hotwords(cfg, skills) if hotwords is None else hotwords,
-                    hotword_boost=g.stt_hotword_boost)
+                    hotword_boost=g.stt_hotword_boost, vad=g.vad_config())
     if llm is None:
         llm = LLMEngine(lcfg, device, seed=g.seed, max_seqs=g.max_batch, weights=lw,
                         max_seq_len=g.max_seq_len, block_size=g.kv_block, use_graphs=g.use_graphs,

@@ -100,6 +100,8 @@ class GPUVoiceProcessor:
                       "progressive": 0, "first_audio_ms_sum": 0.0, "first_audio_n": 0}
         if getattr(getattr(pipeline, "stt", None), "hotwords_on", False):
             self.stats["stt_hotword"] = 0   # utterances whose transcript contains a hotword
+        if getattr(getattr(pipeline, "stt", None), "vad", None) is not None:
+            self.stats["stt_vad_silent"] = 0    # utterances the detector found no speech in
         # a list that collects every finished PipelineJob (phase timestamps for
         # a benchmark's per-phase breakdown); None: not collected
         self.job_sink: list | None = None
@@ -214,6 +216,12 @@ class GPUVoiceProcessor:
                 r.metrics["stt"]["hotwords"] = list(tr.hotwords)
                 if tr.hotwords and "stt_hotword" in self.stats:
                     self.stats["stt_hotword"] += 1
+            if tr.vad_spans is not None:         # the engine runs voice activity detection
+                r.metrics["stt"].update(vad_spans=[list(s) for s in tr.vad_spans],
+                                        vad_speech_s=tr.vad_speech_s, vad_silent=tr.vad_silent)
+                if tr.vad_silent and "stt_vad_silent" in self.stats:
+                    # answered with no_speech below; no encoder, decoder or LLM pass ran
+                    self.stats["stt_vad_silent"] += 1
             if getattr(j, "stt_fallback", False):   # some window was decoded again
                 self.stats["stt_fallback"] += 1
             if j.no_speech:                      # dropped by the no-speech rule: no LLM pass
